@@ -4,10 +4,16 @@ One "step" = forward (encoder -> reparameterise -> decoder) + BCE/KL loss + back
 (N>1: RCCL gradient all-reduce) + Adam, on B synthetic 128x128 fp32 patterns per GPU
 (weak scaling), seeded kaiming-uniform weights of the reference architecture.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 256]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 256] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N ... bench.py --gpus N ...     (N > 1, one rank per GPU)
 
-Prints ONE JSON line (rank 0) with the driver's contract fields plus:
+A plain run sets up, warms up, times the K steps and prints ONE JSON line (rank 0) with the
+driver's contract fields (metric, value, unit, higher_is_better, dtype, ms_per_step, ...).
+--dump-outputs DIR also writes what the last timed step returned and left behind (loss, kl,
+rec, the flat parameters and the flat gradient) as DIR/<name>.npy; weights, patterns and
+noise are seeded, so two runs with the same arguments dump the same step.
+
+--full adds the legs that take work of their own, and their fields on the line:
   roofline      the dominant kernel family (by GPU time), its algorithmic FLOPs per
                 launch / average launch duration (HIP events on the launch stream, live in
                 the timed region on every --probe-every'th step) against the peak of the
@@ -49,6 +55,7 @@ import torch.distributed as dist  # noqa: E402
 
 FP32_PEAK_TFLOPS = 157.3      # MI355X fp32 MFMA (= fp32 vector) dense peak
 HBM_PEAK_GBS = 8000.0
+DUMP_MAX_ELEMS = 6 * 1000 * 1000   # per --dump-outputs array: two large arrays stay under 64 MB
 
 
 def log(*a):
@@ -426,6 +433,23 @@ def strict_fp32_rate(model, x, args, dev, world):
             "dtype": "fp32"}
 
 
+def dump_outputs(path, trainer, out):
+    """--dump-outputs: what the caller of the last timed `trainer.step(x)` holds afterwards,
+    as float32 <name>.npy under `path`: the three loss scalars it returned, and the state it
+    wrote: the flat parameters after Adam and the flat gradient (trainer order: decoder, heads,
+    encoder).  2 x 7.4 MB at the default sizes; an array of more than DUMP_MAX_ELEMS elements
+    (24 MB) is cut to a fixed, seeded sample of that many, in index order."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {"loss": out[0], "kl": out[1], "rec": out[2],
+              "params": trainer.flat, "grads": trainer.gflat}
+    for name, t in arrays.items():
+        a = t.detach().to(torch.float32).cpu().numpy().reshape(-1)
+        if a.size > DUMP_MAX_ELEMS:
+            idx = np.random.default_rng(0).choice(a.size, DUMP_MAX_ELEMS, replace=False)
+            a = a[np.sort(idx)]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def _free_port() -> int:
     import socket
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as s:
@@ -481,6 +505,11 @@ def main():
     ap.add_argument("--batch", type=int, default=256, help="patterns per GPU")
     ap.add_argument("--image-size", type=int, default=128)
     ap.add_argument("--latent-dim", type=int, default=16)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR/<name>.npy (rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure: per-kernel probe and roofline, "
+                         "strict fp32, c5, c4 and the CPU baseline (the options below tune them)")
     ap.add_argument("--cpu-timed", type=int, default=3, help="timed CPU-baseline steps per shape")
     ap.add_argument("--strict-fp32-steps", type=int, default=20,
                     help="timed steps of the strict fp32-MFMA leg (0: skip)")
@@ -557,7 +586,7 @@ def main():
         trainer.step(x)
     torch.cuda.synchronize()
 
-    probe = E.probe() if not args.no_probe else None
+    probe = E.probe() if args.full and not args.no_probe else None
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
@@ -593,6 +622,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t)
     loss = float(out[0])
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, trainer, out)   # before any other leg steps the model
     ms = elapsed / args.steps * 1e3
     value = world * args.batch * args.steps / elapsed
     exposed = trainer.allreduce_exposed_ms()
@@ -675,13 +706,13 @@ def main():
         "loss": round(loss, 6),
         "kernel_families_ms_per_step": {k: round(v["ms"] / max(1, probed), 3) for k, v in fam.items()},
     }
-    if args.strict_fp32_steps > 0:
+    if args.full and args.strict_fp32_steps > 0:
         res["strict_fp32"] = strict_fp32_rate(model, x, args, dev, world)
-    if args.c5_steps > 0 and args.image_size == 128:
+    if args.full and args.c5_steps > 0 and args.image_size == 128:
         res["c5_256"] = c5_step_rate(args, dev, world, rank)
-    if args.c4_batches > 0:
+    if args.full and args.c4_batches > 0:
         res["c4_encoder_latents"] = encoder_latents(model, plan, args, dev, world)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         log("[bench] cpu baseline ...")
         res["cpu_baseline"] = cpu_baseline(plan, args.cpu_timed)
     if rank == 0:

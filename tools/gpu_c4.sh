@@ -13,7 +13,7 @@ LIB=$R/ebsd-vae_amd/lib/libebsdvae.so
 for i in $(seq 1 $NP); do
   for L in new old; do
     if [ $L = new ]; then EY=0; else EY=1; fi
-    EBSDVAE_EVAL_Y=$EY timeout -k 10 200 python3 bench.py --no-cpu-baseline --strict-fp32-steps 0 --c5-steps 0 --steps 10 > $O/b_${T}_${L}_$i.txt 2> $O/b_${T}_${L}_$i.err || exit 1
+    EBSDVAE_EVAL_Y=$EY timeout -k 10 200 python3 bench.py --full --no-cpu-baseline --strict-fp32-steps 0 --c5-steps 0 --steps 10 > $O/b_${T}_${L}_$i.txt 2> $O/b_${T}_${L}_$i.err || exit 1
     echo "bench $L $i $(python3 -c "
 import json;d=json.loads(open('$O/b_${T}_${L}_$i.txt').read().splitlines()[-1]);c=d['c4_encoder_latents']
 print(d['ms_per_step'], c['ms_per_batch'], c['value'], c['engine_only']['value'])")"

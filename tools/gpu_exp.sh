@@ -20,7 +20,7 @@ if [ "$MICRO" != "-" ]; then
 fi
 for i in $(seq 1 $NP); do
   for X in $VALS; do
-    env $VAR=$X timeout -k 10 150 python3 bench.py --no-cpu-baseline --strict-fp32-steps 0 --c4-batches 0 --c5-steps 0 --steps 20 > $O/x_${T}_${X}_$i.txt 2> $O/x_${T}_${X}_$i.err; rc=$?
+    env $VAR=$X timeout -k 10 150 python3 bench.py --full --no-cpu-baseline --strict-fp32-steps 0 --c4-batches 0 --c5-steps 0 --steps 20 > $O/x_${T}_${X}_$i.txt 2> $O/x_${T}_${X}_$i.err; rc=$?
     [ $rc -ne 0 ] && { tail -20 $O/x_${T}_${X}_$i.err; exit $rc; }
     echo "bench $VAR=$X $i $(python3 -c "import json;d=json.loads(open('$O/x_${T}_${X}_$i.txt').read().splitlines()[-1]);print(d['ms_per_step'], d['value'], d['kernel_families_ms_per_step'])")"
   done

@@ -22,7 +22,7 @@ fi
 for i in $(seq 1 $NP); do
   for L in new $V; do
     if [ $L = new ]; then LIB=$NEW; else LIB=$OLD; fi
-    EBSDVAE_LIB=$LIB timeout -k 10 150 python3 bench.py --no-cpu-baseline --strict-fp32-steps 0 --c4-batches 0 --c5-steps 0 --steps 20 > $O/l_${T}_${L}_$i.txt 2> $O/l_${T}_${L}_$i.err; rc=$?
+    EBSDVAE_LIB=$LIB timeout -k 10 150 python3 bench.py --full --no-cpu-baseline --strict-fp32-steps 0 --c4-batches 0 --c5-steps 0 --steps 20 > $O/l_${T}_${L}_$i.txt 2> $O/l_${T}_${L}_$i.err; rc=$?
     [ $rc -ne 0 ] && { tail -20 $O/l_${T}_${L}_$i.err; exit $rc; }
     echo "bench $L $i $(python3 -c "import json;d=json.loads(open('$O/l_${T}_${L}_$i.txt').read().splitlines()[-1]);print(d['ms_per_step'], d['value'], d['kernel_families_ms_per_step'])")"
   done

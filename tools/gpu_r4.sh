@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 O=$R/gpurun_out
 cd $R
 for i in 1 2; do
-  timeout -k 10 200 python3 bench.py --no-cpu-baseline --strict-fp32-steps 0 --c4-batches 0 --c5-steps 0 --steps 20 > $O/b_${T}_$i.txt 2> $O/b_${T}_$i.err || { tail -20 $O/b_${T}_$i.err; exit 1; }
+  timeout -k 10 200 python3 bench.py --full --no-cpu-baseline --strict-fp32-steps 0 --c4-batches 0 --c5-steps 0 --steps 20 > $O/b_${T}_$i.txt 2> $O/b_${T}_$i.err || { tail -20 $O/b_${T}_$i.err; exit 1; }
   echo "bench $i $(python3 -c "import json;d=json.loads(open('$O/b_${T}_$i.txt').read().splitlines()[-1]);print(d['ms_per_step'], d['value'], d['roofline']['frac'])")"
 done
 timeout -k 10 200 python3 tools/layer_profile.py --serial > $O/layers_$T.txt 2>&1 || { tail -20 $O/layers_$T.txt; exit 1; }

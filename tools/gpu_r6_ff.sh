@@ -8,6 +8,7 @@ timeout -k 10 600 python -u -m pytest -x -v --timeout 200 --timeout-method threa
   tests/test_gpu_trainer.py tests/test_gpu_determinism.py tests/test_gpu_fullsize.py -s \
   > gpurun_out/r6_ff_tests2.txt 2>&1 || { echo TESTS2_FAILED; exit 1; }
 timeout -k 10 120 python tools/edge_micro.py --only net_end,net_end_valu > gpurun_out/r6_ne_micro.txt 2>&1 && \
-timeout -k 10 300 python bench.py --no-cpu-baseline --strict-fp32-steps 0 > gpurun_out/r6_ff_on.json 2> gpurun_out/r6_ff_on.err && \
-EBSDVAE_FIRST_FUSE=0 EBSDVAE_NET_END_MFMA=0 timeout -k 10 300 python bench.py --no-cpu-baseline --strict-fp32-steps 0 > gpurun_out/r6_ff_off.json 2> gpurun_out/r6_ff_off.err && \
-timeout -k 10 300 python bench.py --no-cpu-baseline --strict-fp32-steps 0 > gpurun_out/r6_ff_on2.json 2> gpurun_out/r6_ff_on2.err
+O=${O:-$(mktemp -d)} && \
+timeout -k 10 300 python bench.py --full --no-cpu-baseline --strict-fp32-steps 0 > $O/r6_ff_on.json 2> $O/r6_ff_on.err && \
+EBSDVAE_FIRST_FUSE=0 EBSDVAE_NET_END_MFMA=0 timeout -k 10 300 python bench.py --full --no-cpu-baseline --strict-fp32-steps 0 > $O/r6_ff_off.json 2> $O/r6_ff_off.err && \
+timeout -k 10 300 python bench.py --full --no-cpu-baseline --strict-fp32-steps 0 > $O/r6_ff_on2.json 2> $O/r6_ff_on2.err

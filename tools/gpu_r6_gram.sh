@@ -6,6 +6,7 @@ timeout -k 10 400 python -u -m pytest -x -q -s --timeout 200 --timeout-method th
 tail -1 gpurun_out/r6_gram_tests.txt; grep "moments:\|latents, moment" gpurun_out/r6_gram_tests.txt
 for i in 1 2; do for L in default gram1; do
   if [ $L = default ]; then unset EBSDVAE_LIB; else export EBSDVAE_LIB=ebsd-vae_amd/lib/libebsdvae_$L.so; fi
-  timeout -k 10 200 python3 bench.py --no-cpu-baseline --strict-fp32-steps 0 --c5-steps 0 --steps 5 --warmup 2 --no-probe > gpurun_out/gram_$L.txt 2>/dev/null || exit 1
-  echo "$L c4 $(python3 -c "import json;d=json.loads(open('gpurun_out/gram_$L.txt').read().splitlines()[-1]);c=d['c4_encoder_latents'];print(c['ms_per_batch'], c['engine_only']['value'])")"
+  O=${O:-$(mktemp -d)}   # the bench lines go here
+  timeout -k 10 200 python3 bench.py --full --no-cpu-baseline --strict-fp32-steps 0 --c5-steps 0 --steps 5 --warmup 2 --no-probe > $O/gram_$L.txt 2>/dev/null || exit 1
+  echo "$L c4 $(python3 -c "import json;d=json.loads(open('$O/gram_$L.txt').read().splitlines()[-1]);c=d['c4_encoder_latents'];print(c['ms_per_batch'], c['engine_only']['value'])")"
 done; done

@@ -7,6 +7,7 @@ tail -1 gpurun_out/r6_wreg_tests.txt
 for i in 1 2; do for L in default nowreg; do
   if [ $L = default ]; then unset EBSDVAE_LIB; else export EBSDVAE_LIB=ebsd-vae_amd/lib/libebsdvae_$L.so; fi
   timeout -k 10 150 python3 tools/conv_micro.py --pieces 16 --warm 0.5 --only fwd128s8,dgrad128s8 2>&1 | grep -v amdgpu.ids | sed "s/^/$L /" || exit 1
-  timeout -k 10 200 python3 bench.py --no-cpu-baseline --strict-fp32-steps 0 --c4-batches 256 --c5-steps 0 --steps 30 > gpurun_out/wreg_$L.txt 2>/dev/null || exit 1
-  echo "$L bench $(python3 -c "import json;d=json.loads(open('gpurun_out/wreg_$L.txt').read().splitlines()[-1]);print(d['ms_per_step'], d['c4_encoder_latents']['ms_per_batch'])")"
+  O=${O:-$(mktemp -d)}   # the bench lines go here
+  timeout -k 10 200 python3 bench.py --full --no-cpu-baseline --strict-fp32-steps 0 --c4-batches 256 --c5-steps 0 --steps 30 > $O/wreg_$L.txt 2>/dev/null || exit 1
+  echo "$L bench $(python3 -c "import json;d=json.loads(open('$O/wreg_$L.txt').read().splitlines()[-1]);print(d['ms_per_step'], d['c4_encoder_latents']['ms_per_batch'])")"
 done; done
