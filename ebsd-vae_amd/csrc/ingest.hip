@@ -14,6 +14,10 @@
 // Values outside [0, 1] are clamped before the uint8 cast (numpy's out-of-range float->uint8
 // cast is platform-defined); NaN maps to 0.  HBM-bound: one thread per output pixel, reads
 // the source pixel once (8 B for float64), writes 4 B.
+//
+// ebsdvae_ingest_patterns_u8 takes detector data that already is uint8: the same crop / pad
+// geometry and ToTensor's float32(v) / 255 alone (a true division), which is what the float
+// entry point gives for v / 255.0 -- (v / 255.0) * 255.0 truncates back to v for all 256 values.
 #include "common.h"
 #include "../../include/ebsdvae.h"
 
@@ -49,6 +53,23 @@ __global__ __launch_bounds__(256) void ingest_kernel(const T* __restrict__ src, 
   dst[i] = out;
 }
 
+__global__ __launch_bounds__(256) void ingest_u8_kernel(const unsigned char* __restrict__ src,
+                                                        int H0, int W0, int oh, int ow, int top,
+                                                        int left, long long n,
+                                                        float* __restrict__ dst) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int x = (int)(i % ow);
+  const long long r = i / ow;
+  const int y = (int)(r % oh);
+  const long long b = r / oh;
+  const int sy = y + top, sx = x + left;
+  float out = 0.f;
+  if (sy >= 0 && sy < H0 && sx >= 0 && sx < W0)
+    out = (float)src[(b * H0 + sy) * W0 + sx] / 255.0f;
+  dst[i] = out;
+}
+
 }  // namespace ev
 
 using namespace ev;
@@ -69,4 +90,17 @@ extern "C" int ebsdvae_ingest_patterns(const void* src, int src_dtype, int B, in
     hipLaunchKernelGGL(ingest_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream,
                        (const float*)src, H0, W0, out_h, out_w, top, left, n, dst);
   return evh::check_launch("ingest_patterns");
+}
+
+extern "C" int ebsdvae_ingest_patterns_u8(const unsigned char* src, int B, int H0, int W0,
+                                          int out_h, int out_w, float* dst,
+                                          ebsdvae_stream_t stream) {
+  EV_REQUIRE(src && dst && B >= 0 && H0 > 0 && W0 > 0 && out_h > 0 && out_w > 0,
+             "ingest_patterns_u8: bad args");
+  if (B == 0) return 0;
+  const long long n = (long long)B * out_h * out_w;
+  const int top = crop_offset(H0, out_h), left = crop_offset(W0, out_w);
+  hipLaunchKernelGGL(ingest_u8_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
+                     (hipStream_t)stream, src, H0, W0, out_h, out_w, top, left, n, dst);
+  return evh::check_launch("ingest_patterns_u8");
 }

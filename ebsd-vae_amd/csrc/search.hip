@@ -16,85 +16,10 @@
 // Chunks' lists are merged per query by the same insertion in a second launch, then
 // bitonic-sorted across the wave.  Ties break to the lower row index (deterministic).
 #include "common.h"
+#include "topk.h"
 #include "../../include/ebsdvae.h"
 
-#include <float.h>
-
 namespace ev {
-
-constexpr int TK_WAVES = 4;     // waves per block (each its own query group, same chunk)
-constexpr int TK_MAXK = 64;
-constexpr int TK_MAXD = 64;
-
-// (s, i) beats (t, j)
-EV_DEVINL bool tk_better(float s, int i, float t, int j) { return s > t || (s == t && i < j); }
-
-// running top-k of one query in one wave: lane l < k holds slot l
-struct TopK {
-  float v;
-  int i;
-  float thr;   // wave-uniform: the worst kept slot (admission threshold)
-  int thr_i;
-  int thr_lane;
-};
-
-EV_DEVINL void tk_init(TopK& t, int k, int lane) {
-  t.v = -FLT_MAX;
-  t.i = 0x7fffffff;
-  (void)k;
-  (void)lane;
-  t.thr = -FLT_MAX;
-  t.thr_i = 0x7fffffff;
-  t.thr_lane = 0;
-}
-
-// recompute the worst slot among lanes < k (wave reduction, ties -> larger index is worse)
-EV_DEVINL void tk_refresh(TopK& t, int k, int lane) {
-  float v = lane < k ? t.v : FLT_MAX;
-  int i = lane < k ? t.i : -1;
-  int l = lane;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float v2 = __shfl_xor(v, o, 64);
-    const int i2 = __shfl_xor(i, o, 64);
-    const int l2 = __shfl_xor(l, o, 64);
-    // keep the WORSE of the two (the one the other beats)
-    if (tk_better(v, i, v2, i2) || (v == v2 && i == i2 && l2 < l)) { v = v2; i = i2; l = l2; }
-  }
-  t.thr = v;
-  t.thr_i = i;
-  t.thr_lane = l;
-}
-
-// offer candidate (s, idx) held by each lane (valid where ok); inserts the qualifying ones
-EV_DEVINL void tk_offer(TopK& t, float s, int idx, bool ok, int k, int lane) {
-  unsigned long long m = __ballot(ok && tk_better(s, idx, t.thr, t.thr_i));
-  while (m) {
-    const int src = __builtin_ctzll(m);
-    m &= m - 1;
-    const float cs = __shfl(s, src, 64);
-    const int ci = __shfl(idx, src, 64);
-    if (!tk_better(cs, ci, t.thr, t.thr_i)) continue;   // threshold rose meanwhile
-    if (lane == t.thr_lane) { t.v = cs; t.i = ci; }
-    tk_refresh(t, k, lane);
-  }
-}
-
-// bitonic sort of the 64 lanes' (v, i), best first (slots >= k hold -FLT_MAX / INT_MAX)
-EV_DEVINL void tk_sort(float& v, int& i, int lane) {
-#pragma unroll
-  for (int size = 2; size <= 64; size <<= 1) {
-#pragma unroll
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      const float v2 = __shfl_xor(v, stride, 64);
-      const int i2 = __shfl_xor(i, stride, 64);
-      const bool asc = (lane & size) == 0;          // this block orders best-first
-      const bool lower = (lane & stride) == 0;
-      const bool take = (lower == asc) ? tk_better(v2, i2, v, i) : tk_better(v, i, v2, i2);
-      if (take) { v = v2; i = i2; }
-    }
-  }
-}
 
 __global__ __launch_bounds__(256) void l2norm_rows_kernel(const float* __restrict__ x,
                                                           float* __restrict__ y, long long n, int d) {
@@ -166,27 +91,16 @@ __global__ __launch_bounds__(64) void topk_merge_kernel(const float* __restrict_
                                                         float* __restrict__ out_s,
                                                         long long* __restrict__ out_i) {
   const int q = blockIdx.x, lane = threadIdx.x;
-  TopK t;
-  tk_init(t, k, lane);
-  const size_t base = (size_t)q * nchunk * k;
-  const int total = nchunk * k;
-  for (int c0 = 0; c0 < total; c0 += 64) {
-    const int c = c0 + lane;
-    const bool ok = c < total;
-    const float s = ok ? ps[base + c] : -FLT_MAX;
-    const int i = ok ? pi[base + c] : 0x7fffffff;
-    tk_offer(t, s, i, ok && i != 0x7fffffff, k, lane);
-  }
-  float v = lane < k ? t.v : -FLT_MAX;
-  int i = lane < k ? t.i : 0x7fffffff;
-  tk_sort(v, i, lane);
+  float v;
+  int i;
+  tk_merge_sorted(ps, pi, q, nchunk, k, lane, v, i);
   if (lane < k) {
     out_s[(size_t)q * k + lane] = v;
     out_i[(size_t)q * k + lane] = (i == 0x7fffffff) ? -1 : (long long)i;
   }
 }
 
-static int topk_chunks(long long N, int Q, int d) {
+int topk_chunks(long long N, int Q, int d) {
   // enough (chunk, query-group) waves to fill the chip, chunks of >= 512 rows
   const int qw = 64 / d;
   const int qg = (Q + qw * TK_WAVES - 1) / (qw * TK_WAVES);
@@ -196,6 +110,19 @@ static int topk_chunks(long long N, int Q, int d) {
   if (c < 1) c = 1;
   if (c > 4096) c = 4096;
   return (int)c;
+}
+
+void topk_launch_chunks(const float* db, long long N, const float* queries, int Q, int d, int k,
+                        int nc, float* ps, int* pi, hipStream_t s) {
+  const long long rpc = (N + nc - 1) / nc;
+  const int qw = 64 / d;
+  const dim3 grid(nc, (Q + qw * TK_WAVES - 1) / (qw * TK_WAVES));
+  if (d == 16)
+    hipLaunchKernelGGL(topk_chunk_kernel<16>, grid, dim3(256), 0, s, db, N, queries, Q, k, rpc, nc, ps, pi);
+  else if (d == 32)
+    hipLaunchKernelGGL(topk_chunk_kernel<32>, grid, dim3(256), 0, s, db, N, queries, Q, k, rpc, nc, ps, pi);
+  else
+    hipLaunchKernelGGL(topk_chunk_kernel<64>, grid, dim3(256), 0, s, db, N, queries, Q, k, rpc, nc, ps, pi);
 }
 
 }  // namespace ev
@@ -225,18 +152,10 @@ extern "C" int ebsdvae_cosine_topk(const float* db, long long N, const float* qu
   EV_REQUIRE(k >= 1 && k <= TK_MAXK && k <= N, "cosine_topk: k=%d (1..%d, <= N)", k, TK_MAXK);
   EV_REQUIRE(d == 16 || d == 32 || d == 64, "cosine_topk: d=%d (16, 32 or 64)", d);
   const int nc = topk_chunks(N, Q, d);
-  const long long rpc = (N + nc - 1) / nc;
   float* ps = reinterpret_cast<float*>(work);
   int* pi = reinterpret_cast<int*>(ps + (size_t)Q * nc * k);
-  const int qw = 64 / d;
-  const dim3 grid(nc, (Q + qw * TK_WAVES - 1) / (qw * TK_WAVES));
   hipStream_t s = (hipStream_t)stream;
-  if (d == 16)
-    hipLaunchKernelGGL(topk_chunk_kernel<16>, grid, dim3(256), 0, s, db, N, queries, Q, k, rpc, nc, ps, pi);
-  else if (d == 32)
-    hipLaunchKernelGGL(topk_chunk_kernel<32>, grid, dim3(256), 0, s, db, N, queries, Q, k, rpc, nc, ps, pi);
-  else
-    hipLaunchKernelGGL(topk_chunk_kernel<64>, grid, dim3(256), 0, s, db, N, queries, Q, k, rpc, nc, ps, pi);
+  topk_launch_chunks(db, N, queries, Q, d, k, nc, ps, pi, s);
   hipLaunchKernelGGL(topk_merge_kernel, dim3(Q), dim3(64), 0, s, ps, pi, nc, k, out_scores, out_idx);
   return evh::check_launch("cosine_topk");
 }

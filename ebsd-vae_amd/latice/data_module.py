@@ -76,6 +76,32 @@ def ingest_patterns(raw, image_size=(128, 128), device="cuda", out: torch.Tensor
     return out
 
 
+def ingest_patterns_u8(raw, image_size=(128, 128), device="cuda", out: torch.Tensor | None = None):
+    """The same transform for detector data that already is uint8: raw (B, H0, W0) uint8 ->
+    (B, 1, h, w) float32 = float32(v) / 255 after the centre crop / zero pad, bit-identical to
+    `ingest_patterns(raw / 255.0)`.  (`ingest_patterns` itself reads a uint8 array as raw
+    values, as the reference's astype(float64) does, and clamps them to 1.)"""
+    t = torch.as_tensor(raw)
+    if t.dtype != torch.uint8:
+        raise TypeError(f"ingest_patterns_u8 needs uint8 patterns, got {t.dtype}")
+    if t.ndim == 2:
+        t = t.unsqueeze(0)
+    if t.ndim != 3:
+        raise ValueError(f"patterns must be (B, H, W), got {tuple(t.shape)}")
+    t = t.to(device, non_blocking=True).contiguous()
+    if not t.is_cuda:
+        raise RuntimeError("ingest_patterns_u8 needs a ROCm device (no CPU fallback)")
+    B, H0, W0 = t.shape
+    h, w = image_size
+    if out is None:
+        out = torch.empty(B, 1, h, w, dtype=torch.float32, device=t.device)
+    elif out.numel() != B * h * w or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous ({B}, 1, {h}, {w}) tensor, got {tuple(out.shape)}")
+    N.call("ebsdvae_ingest_patterns_u8", t.data_ptr(), B, H0, W0, h, w, N.ptr(out),
+           N.stream(t.device))
+    return out
+
+
 class PatternTransform:
     """What `create_default_transform(image_size)` returns (data_module.py:17-33): called on
     one pattern -- an (H, W) or (1, H, W) array or tensor -- it returns the (1, h, w) float32

@@ -13,6 +13,10 @@ path: same `IndexerConfig` and `DiffractionPatternIndexer` API and call contract
   add_vectors / find_best_orientation / find_best_orientations_batch can be passed as `db`.
 * encode_patterns_batch transforms a numpy stack in ONE launch when the transform is the
   default one (the reference loops per pattern, :149-163).
+* `index_scan` has no counterpart in the reference: a whole scan (a .npy path, a host array of
+  float or uint8 patterns, or a transformed device tensor) streams through pinned staging
+  buffers, ingest, `encode_mu` and `db.index_latents`, and comes back as one
+  `ScanIndexResult` of numpy arrays (latice/index/scan.py).
 """
 from __future__ import annotations
 
@@ -25,14 +29,18 @@ import numpy as np
 import torch
 from pydantic.dataclasses import dataclass
 
-from latice.data_module import DPDataModule, PatternTransform, create_default_transform
-from latice.index.faiss_db import (FaissLatentVectorDatabase, FaissLatentVectorDatabaseConfig,
+from latice.data_module import (DPDataModule, PatternTransform, create_default_transform,
+                                ingest_patterns, ingest_patterns_u8)
+from latice.index.faiss_db import (MAX_K, FaissLatentVectorDatabase,
+                                   FaissLatentVectorDatabaseConfig, LatentIndexResult,
                                    OrientationResult)
+from latice.index.scan import (SCAN_F32, SCAN_F64, SCAN_U8, ScanIndexResult, open_scan,
+                               scan_batches)
 from latice.model import VariationalAutoEncoder
 
 logger = logging.getLogger(__name__)
 
-__all__ = ["IndexerConfig", "DiffractionPatternIndexer", "OrientationResult"]
+__all__ = ["IndexerConfig", "DiffractionPatternIndexer", "OrientationResult", "ScanIndexResult"]
 
 
 @dataclass
@@ -155,6 +163,131 @@ class DiffractionPatternIndexer:
         latent_vectors = self.encode_patterns_batch(patterns)
         return self.db.find_best_orientations_batch(latent_vectors, batch_size=self.config.batch_size,
                                                     **kwargs)
+
+    def index_scan(self, patterns, top_n: int | None = None,
+                   orientation_threshold: float | None = None, min_required_matches: int = 18,
+                   max_iterations: int = 3, batch_size: int | None = None,
+                   return_candidates: bool = False) -> ScanIndexResult:
+        """A whole scan in, an orientation map out, everything between on the device.
+
+        `patterns` is a path to a .npy file (memory-mapped), a numpy array / memmap
+        (N, H0, W0) of float64, float32 (the DPdataset transform, `ingest_patterns`) or uint8
+        (detector data, `ingest_patterns_u8`: v / 255), or a device tensor (N, 1, h, w)
+        float32 that is already transformed.  Per batch: host slice -> one of two pinned
+        staging buffers -> async copy on a copy stream -> ingest -> `model.encode_mu` ->
+        `db.index_latents` into result arrays preallocated for all N patterns (44 B per
+        pattern without candidates).  The host waits only for a staging buffer to be free
+        again, never for a batch's results; the results come back in one copy at the end."""
+        top_n = top_n or self.config.top_n
+        orientation_threshold = orientation_threshold or self.config.orientation_threshold
+        batch_size = int(batch_size or self.config.batch_size)
+        if not callable(getattr(self.db, "index_latents", None)):
+            raise TypeError(f"index_scan needs a database with index_latents(latents, ..., out=) "
+                            f"that works on device tensors (FaissLatentVectorDatabase); "
+                            f"{type(self.db).__name__} has none")
+        if top_n > MAX_K:
+            raise ValueError(f"top_n={top_n} > {MAX_K} (GPU top-k limit)")
+        if batch_size < 1:
+            raise ValueError(f"batch_size={batch_size} must be at least 1")
+        kw = dict(top_n=top_n, orientation_threshold=orientation_threshold,
+                  min_required_matches=min_required_matches, max_iterations=max_iterations)
+        on_device = torch.is_tensor(patterns)
+        if on_device:
+            if not (patterns.is_cuda and patterns.dim() == 4 and patterns.shape[1] == 1
+                    and patterns.dtype == torch.float32):
+                raise ValueError("a tensor scan must be a transformed (N, 1, h, w) float32 device "
+                                 f"tensor, got {tuple(patterns.shape)} {patterns.dtype} on "
+                                 f"{patterns.device}")
+            n, dev = patterns.shape[0], patterns.device
+        else:
+            patterns = open_scan(patterns)
+            items = scan_batches(patterns, batch_size)
+            n, dev = patterns.shape[0], self.device
+        k = min(top_n, self.db.get_count()) if return_candidates else 0
+
+        # every result array is a view of ONE device buffer, so one copy brings them all
+        # back; the 8-byte fields come first to keep every view aligned
+        fields = [("best", torch.float64, (n, 3)), ("row", torch.int64, (n,))]
+        if return_candidates:
+            fields.append(("cand_idx", torch.int64, (n, k)))
+        fields += [("score", torch.float32, (n,)), ("success", torch.int32, (n,)),
+                   ("n_similar", torch.int32, (n,))]
+        if return_candidates:
+            fields.append(("cand_scores", torch.float32, (n, k)))
+        sizes = [int(np.prod(shape)) * torch.empty((), dtype=dt).element_size()
+                 for _, dt, shape in fields]
+        offsets = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        buf = torch.empty(max(int(offsets[-1]), 8), dtype=torch.uint8, device=dev)
+
+        def carve(raw, to_view):
+            return {name: to_view(raw[int(o):int(o) + sz], dt, shape)
+                    for (name, dt, shape), o, sz in zip(fields, offsets, sizes)}
+
+        staging = None
+        res = LatentIndexResult(**carve(buf, lambda b, dt, shape: b.view(dt).view(shape)))
+
+        if on_device:
+            for s in range(0, n, batch_size):
+                e = min(s + batch_size, n)
+                self.db.index_latents(self.model.encode_mu(patterns[s:e]), out=res.slice(s, e), **kw)
+        elif n:
+            staging = self._stream_scan(patterns, items, batch_size, dev, res, kw)
+
+        host = buf.cpu().numpy()     # the one device-to-host copy (and the only host wait)
+        del staging                  # every copy-stream buffer outlived its last consumer
+        np_dt = {torch.float64: np.float64, torch.int64: np.int64, torch.float32: np.float32,
+                 torch.int32: np.int32}
+        h = carve(host, lambda b, dt, shape: b.view(np_dt[dt]).reshape(shape))
+        return ScanIndexResult(orientations=h["best"], success=h["success"].astype(bool),
+                               scores=h["score"], top_index=h["row"], n_similar=h["n_similar"],
+                               candidate_indices=h.get("cand_idx"),
+                               candidate_scores=h.get("cand_scores"))
+
+    def _stream_scan(self, patterns, items, batch_size, dev, res, kw):
+        """The host half of index_scan: batch i is copied from the scan into pinned buffer
+        i & 1, then to device buffer i & 1 on a copy stream, while the compute stream still
+        works on batch i - 1.  Events order the two streams in both directions; the host
+        waits only for `copied[j]` (the copy out of the pinned buffer it is about to refill).
+        The staging buffers are returned: the caller keeps them alive until its result copy
+        has synchronised the compute stream, which has waited for every copy."""
+        per = tuple(patterns.shape[1:])
+        code = items[0][2]
+        th_dt = {SCAN_F64: torch.float64, SCAN_F32: torch.float32, SCAN_U8: torch.uint8}[code]
+        shape = (min(batch_size, patterns.shape[0]),) + per
+        h, w = self.config.image_size
+        with torch.cuda.device(dev):
+            compute = torch.cuda.current_stream(dev)
+            copy = torch.cuda.Stream(dev)
+            pinned = [torch.empty(shape, dtype=th_dt).pin_memory() for _ in range(2)]
+            pinned_np = [p.numpy() for p in pinned]
+            staged = [torch.empty(shape, dtype=th_dt, device=dev) for _ in range(2)]
+            x = torch.empty(shape[0], 1, h, w, dtype=torch.float32, device=dev)
+            # the allocator may hand out blocks with work still pending on the compute stream
+            begun = torch.cuda.Event()
+            begun.record(compute)
+            copy.wait_event(begun)
+            copied = [None, None]     # copy stream: pinned[j] -> staged[j] finished
+            ingested = [None, None]   # compute stream: the ingest that read staged[j] finished
+            for i, (s, e, _) in enumerate(items):
+                j, m = i & 1, e - s
+                if copied[j] is not None:
+                    copied[j].synchronize()          # pinned[j] is free to refill
+                np.copyto(pinned_np[j][:m], patterns[s:e], casting="unsafe")
+                if ingested[j] is not None:
+                    copy.wait_event(ingested[j])     # staged[j] is free to overwrite
+                with torch.cuda.stream(copy):
+                    staged[j][:m].copy_(pinned[j][:m], non_blocking=True)
+                copied[j] = torch.cuda.Event()
+                copied[j].record(copy)
+                compute.wait_event(copied[j])
+                if code == SCAN_U8:
+                    ingest_patterns_u8(staged[j][:m], (h, w), dev, out=x[:m])
+                else:
+                    ingest_patterns(staged[j][:m], (h, w), dev, out=x[:m])
+                ingested[j] = torch.cuda.Event()
+                ingested[j].record(compute)
+                self.db.index_latents(self.model.encode_mu(x[:m]), out=res.slice(s, e), **kw)
+        return pinned, staged, x
 
     @cached_property
     def _create_dataloader(self):

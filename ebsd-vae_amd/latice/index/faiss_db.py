@@ -8,6 +8,8 @@ as an N x D fp32 tensor and queries run as batched HIP launches (csrc/search.hip
     ebsdvae_l2_normalize_rows   faiss_db.py:107-111 (norm 0 -> 1)
     ebsdvae_cosine_topk         IndexFlatIP.search: k best by score, ties to the lower row
     ebsdvae_orient_consensus    find_best_orientation (:258-398), all queries in one launch
+    ebsdvae_index_latents       the two above without the launch boundary (csrc/scan_index.hip):
+                                `index_latents`, device tensors in and out, for whole scans
 
 There is no CPU or faiss fallback: the dictionary must sit on a ROCm device.  Persistence
 is one .npz with the normalised `latents` and the `orientations` (the reference pickles a
@@ -54,6 +56,44 @@ class OrientationResult:
             return self.candidate_orientations[: min(n, len(self.candidate_orientations))]
         order = np.argsort(self.distances)
         return self.candidate_orientations[order[: min(n, len(order))]]
+
+
+@dataclass
+class LatentIndexResult:
+    """What `FaissLatentVectorDatabase.index_latents` returns, as device tensors: one row per
+    query, no per-query objects.  The candidate lists are None unless asked for."""
+    best: torch.Tensor          # (Q, 3) float64: consensus mean on success, else candidate 0
+    success: torch.Tensor       # (Q,) int32 0/1
+    score: torch.Tensor         # (Q,) float32: cosine of the best match
+    row: torch.Tensor           # (Q,) int64: its dictionary row (-1: empty dictionary)
+    n_similar: torch.Tensor     # (Q,) int32: candidates within the threshold of the last reference
+    cand_scores: torch.Tensor | None = None   # (Q, k) float32, best first
+    cand_idx: torch.Tensor | None = None      # (Q, k) int64
+
+    _SPEC = (("best", torch.float64, 3), ("success", torch.int32, None),
+             ("score", torch.float32, None), ("row", torch.int64, None),
+             ("n_similar", torch.int32, None))
+
+    def check(self, Q: int, k: int, device) -> None:
+        """The kernel writes through raw pointers: every field must be a contiguous tensor of
+        exactly the expected dtype and shape on `device`."""
+        spec = [(n, dt, (Q,) if c is None else (Q, c)) for n, dt, c in self._SPEC]
+        for n, dt in (("cand_scores", torch.float32), ("cand_idx", torch.int64)):
+            if getattr(self, n) is not None:
+                spec.append((n, dt, (Q, k)))
+        for n, dt, shape in spec:
+            t = getattr(self, n)
+            if not (torch.is_tensor(t) and t.dtype == dt and tuple(t.shape) == shape
+                    and t.is_contiguous() and t.device == device):
+                raise ValueError(f"out.{n} must be a contiguous {dt} tensor of shape {shape} "
+                                 f"on {device}")
+
+    def slice(self, start: int, stop: int) -> LatentIndexResult:
+        """Rows [start, stop) of every field (views)."""
+        def cut(t):
+            return None if t is None else t[start:stop]
+        return LatentIndexResult(cut(self.best), cut(self.success), cut(self.score), cut(self.row),
+                                 cut(self.n_similar), cut(self.cand_scores), cut(self.cand_idx))
 
 
 def _as_device_f32(x, device) -> torch.Tensor:
@@ -270,6 +310,67 @@ class FaissLatentVectorDatabase:
             np.asarray(query_vector).reshape(1, -1), top_n=top_n,
             orientation_threshold=orientation_threshold,
             min_required_matches=min_required_matches, max_iterations=max_iterations)[0]
+
+    # ------------------------------------------------------------------ whole-scan indexing
+    def index_latents(self, latents: torch.Tensor, top_n: int = 20,
+                      orientation_threshold: float = 1.0, min_required_matches: int = 18,
+                      max_iterations: int = 3, return_candidates: bool = False,
+                      out: LatentIndexResult | None = None) -> LatentIndexResult:
+        """Search + consensus for a device tensor of (Q, d) latents (not normalised), all on
+        the device: one L2-normalise launch and `ebsdvae_index_latents` (csrc/scan_index.hip).
+        Returns device tensors -- best (Q, 3) f64, success (Q,) int32, score (Q,) f32 and row
+        (Q,) i64 of the top match, n_similar (Q,) int32, and with `return_candidates` the
+        (Q, k) candidate scores and rows, k = min(top_n, count) -- equal bit for bit to what
+        `find_best_orientations_batch` reports for the same latents.  `out` (a
+        LatentIndexResult of contiguous caller-owned tensors, e.g. row slices of whole-scan
+        arrays) is written in place and returned.  No host synchronisation, no per-query
+        objects.  An empty dictionary gives success 0, best NaN, row -1."""
+        if not (torch.is_tensor(latents) and latents.is_cuda):
+            raise RuntimeError("index_latents needs a ROCm device tensor (no CPU fallback)")
+        if top_n > MAX_K:
+            raise ValueError(f"top_n={top_n} > {MAX_K} (GPU top-k limit)")
+        if top_n < 1:
+            raise ValueError(f"top_n={top_n} must be at least 1")
+        q = latents.reshape(-1, latents.shape[-1])
+        if q.shape[1] != self.dimension:
+            raise ValueError(f"Expected latents of dimension {self.dimension}, got {q.shape[1]}")
+        Q, count = q.shape[0], self.get_count()
+        k = min(int(top_n), count)
+        dev = q.device
+        if dev != self._cap_db.device:
+            raise ValueError(f"latents are on {dev}, the dictionary on {self._cap_db.device}")
+        if out is None:
+            out = LatentIndexResult(
+                best=torch.empty(Q, 3, dtype=torch.float64, device=dev),
+                success=torch.empty(Q, dtype=torch.int32, device=dev),
+                score=torch.empty(Q, dtype=torch.float32, device=dev),
+                row=torch.empty(Q, dtype=torch.int64, device=dev),
+                n_similar=torch.empty(Q, dtype=torch.int32, device=dev),
+                cand_scores=torch.empty(Q, k, dtype=torch.float32, device=dev) if return_candidates else None,
+                cand_idx=torch.empty(Q, k, dtype=torch.int64, device=dev) if return_candidates else None)
+        else:
+            out.check(Q, k, dev)
+        if Q == 0:
+            return out
+        if count == 0:
+            out.best.fill_(float("nan"))
+            out.success.zero_()
+            out.score.fill_(float("nan"))
+            out.row.fill_(-1)
+            out.n_similar.zero_()
+            return out
+        qn = l2_normalize(q)
+        nbytes = N.call("ebsdvae_index_latents_work", count, Q, self.dimension, k)
+        work = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=dev)
+        N.call("ebsdvae_index_latents", self._db.data_ptr(), count, self._ori_dev.data_ptr(),
+               qn.data_ptr(), Q, self.dimension, k, float(orientation_threshold),
+               int(min_required_matches), int(max_iterations), out.best.data_ptr(),
+               out.success.data_ptr(), out.score.data_ptr(), out.row.data_ptr(),
+               out.n_similar.data_ptr(),
+               out.cand_scores.data_ptr() if out.cand_scores is not None else None,
+               out.cand_idx.data_ptr() if out.cand_idx is not None else None,
+               work.data_ptr(), N.stream(dev))
+        return out
 
     # ------------------------------------------------------------------ bookkeeping
     def get_count(self) -> int:

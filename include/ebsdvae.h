@@ -530,6 +530,30 @@ int ebsdvae_orient_consensus(const double* orientations, const long long* cand_i
  * dst (B, 1, out_h, out_w).  Values outside [0, 1] are clamped before the uint8 cast. */
 int ebsdvae_ingest_patterns(const void* src, int src_dtype, int B, int H0, int W0, int out_h,
                             int out_w, float* dst, ebsdvae_stream_t stream);
+/* The same transform for patterns that already are uint8 (detector data): the crop / pad
+ * geometry above and ToTensor's float32(v) / 255 (a true division).  Bit-identical to
+ * ebsdvae_ingest_patterns fed v / 255.0 as float64. */
+int ebsdvae_ingest_patterns_u8(const unsigned char* src, int B, int H0, int W0, int out_h,
+                               int out_w, float* dst, ebsdvae_stream_t stream);
+
+/* ---- whole-scan indexing: search + consensus in one call ------------------------------
+ * ebsdvae_cosine_topk followed by ebsdvae_orient_consensus without the launch boundary
+ * between them: the wave that merges a query's top-k list (candidate l in lane l) loads
+ * orientations[row] and runs the consensus.  Same limits (d 16, 32 or 64; 1 <= k <= 64,
+ * k <= N), same arithmetic, and every output equals the two calls' bit for bit.  Per query q:
+ * best[q][3] (the consensus mean on success, else candidate 0), success[q] (0/1),
+ * top_score[q] / top_row[q] (the best match), n_similar[q] (popcount of the similar_mask
+ * ebsdvae_orient_consensus would write).  cand_scores / cand_idx (Q x k, match order) are
+ * written only when non-NULL.  queries are already L2-normalised.  work: device scratch of
+ * ebsdvae_index_latents_work(N, Q, d, k) bytes.  A query's outputs do not depend on the
+ * other queries of the call. */
+size_t ebsdvae_index_latents_work(long long N, int Q, int d, int k);
+int ebsdvae_index_latents(const float* db, long long N, const double* orientations,
+                          const float* queries, int Q, int d, int k, double threshold_deg,
+                          int min_matches, int max_iterations, double* best, int* success,
+                          float* top_score, long long* top_row, int* n_similar,
+                          float* cand_scores, long long* cand_idx, void* work,
+                          ebsdvae_stream_t stream);
 
 #ifdef __cplusplus
 }
