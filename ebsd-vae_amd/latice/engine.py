@@ -27,6 +27,9 @@ from dataclasses import dataclass, field
 import torch
 
 from . import _native as N
+from . import side
+from .side import (cu_split_main, deferred_side_join, fork_arm, serial_streams,  # noqa: F401
+                   side_stream, side_streams_enabled, stream_wait)
 
 ACT_RAW, ACT_NORM, ACT_NORM_POOL, ACT_UP, ACT_NORM_UP = range(5)
 P_ID, P_POOL, P_UP = range(3)
@@ -641,178 +644,7 @@ def _in_bwd_stats(B, C, T, HW, part, like):
     return bst
 
 
-# ----------------------------------------------------------------------------- side stream
-# Weight gradients are off the backward's critical path (in_backward -> input gradient -> ...):
-# they run on a second HIP stream, so they overlap the memory-bound InstanceNorm-backward passes
-# and the other kernels' tails.  The side stream waits for the main stream before each weight
-# gradient (its inputs are ready), and the batched slice reductions run on the side stream too,
-# behind the weight gradients they sum.  The main stream waits for the side stream once, at
-# the next join: at the end of a batched_wgrad_reduce() block, or -- inside
-# deferred_side_join() (the trainer's backward) -- only when that block exits.
-# Buffers the side stream touches are kept alive on the host until that join (no
-# record_stream: its event records on every free cost the GPU idle time at each join).
-# EBSDVAE_WGRAD_STREAM=0 keeps everything on the current stream.
-_WG_STREAM = os.environ.get("EBSDVAE_WGRAD_STREAM", "1") != "0"
-# Inside a hipGraph capture the side stream forks from and joins back into the capturing
-# stream (event edges in the graph).  EBSDVAE_GRAPH_SIDE=0 captures on one stream instead.
-_GRAPH_SIDE = os.environ.get("EBSDVAE_GRAPH_SIDE", "1") != "0"
-_SIDE = {}
-_KEEP = {}    # device -> buffers the side stream uses, released at the join (None: not in use)
-_DEFER = 0    # > 0 inside deferred_side_join()
-
-
-_SERIAL = 0   # > 0 inside serial_streams()
-
-
-@contextlib.contextmanager
-def serial_streams():
-    """Keep the weight gradients on the current stream (no overlap), e.g. while per-launch
-    durations are being measured: overlapped launches would each be timed with the other's
-    work inside (bench.py's probed steps)."""
-    global _SERIAL
-    _SERIAL += 1
-    try:
-        yield
-    finally:
-        _SERIAL -= 1
-
-
-def _dev_key(device):
-    return device.index if device.index is not None else torch.cuda.current_device()
-
-
-# EBSDVAE_CU_SPLIT=k (experiment, DESIGN.md section 6): the weight-gradient side stream runs on
-# k compute units (CU-mask bits [N - k, N), N / 8 of them on every XCD) and cu_split_main()
-# gives the complementary N - k for the input-gradient chain, whose persistent conv kernels then
-# launch N - k blocks (ebsdvae_stream_create_cus).  The caller runs the step on that stream.
-_CU_SPLIT = int(os.environ.get("EBSDVAE_CU_SPLIT", "0"))
-_CU_MAIN = {}
-
-
-def _cu_stream(device, first, count):
-    import ctypes as C
-    out = C.c_void_p()
-    with torch.cuda.device(device):
-        N.call("ebsdvae_stream_create_cus", first, count, C.byref(out))
-    return torch.cuda.ExternalStream(out.value, device=device)
-
-
-def cu_split_main(device):
-    """The CU-partitioned main stream of `device` under EBSDVAE_CU_SPLIT (None otherwise)."""
-    if _CU_SPLIT <= 0:
-        return None
-    key = _dev_key(device)
-    if key not in _CU_MAIN:
-        ncu = torch.cuda.get_device_properties(key).multi_processor_count
-        _CU_MAIN[key] = _cu_stream(torch.device("cuda", key), 0, ncu - _CU_SPLIT)
-    return _CU_MAIN[key]
-
-
-def side_stream(device):
-    """The weight-gradient side stream of `device` (created on first use; CU-masked to
-    EBSDVAE_CU_SPLIT compute units when set)."""
-    key = _dev_key(device)
-    if key not in _SIDE:
-        if _CU_SPLIT > 0:
-            ncu = torch.cuda.get_device_properties(key).multi_processor_count
-            _SIDE[key] = _cu_stream(torch.device("cuda", key), ncu - _CU_SPLIT, _CU_SPLIT)
-        else:
-            _SIDE[key] = torch.cuda.Stream(device=device)
-    return _SIDE[key]
-
-
-def side_streams_enabled() -> bool:
-    """Work may go to the side stream now (not disabled, not inside serial_streams(), and not
-    a capture that keeps everything on one stream)."""
-    if not _WG_STREAM or _SERIAL:
-        return False
-    return _GRAPH_SIDE or not torch.cuda.is_current_stream_capturing()
-
-
-def _side_stream(device):
-    if not _WG_STREAM or _SERIAL:
-        return None
-    if not _GRAPH_SIDE and torch.cuda.is_current_stream_capturing():
-        return None
-    return side_stream(device)
-
-
-# EBSDVAE_LIGHT_EVENTS=0: fork / join through torch's Stream.wait_stream (system-scope fence)
-_LIGHT_EVENTS = os.environ.get("EBSDVAE_LIGHT_EVENTS", "1") != "0"
-
-
-def stream_wait(waiter, signaler):
-    """`waiter` (a torch Stream) waits for the work enqueued on `signaler` so far."""
-    if _LIGHT_EVENTS:
-        N.call("ebsdvae_stream_wait", waiter.cuda_stream, signaler.cuda_stream)
-    else:
-        waiter.wait_stream(signaler)
-
-
-# EBSDVAE_KFORK=0: every fork records an event on the main stream (A/B).  Otherwise the
-# backward arms a kernel-attached fork before each InstanceNorm-backward apply whose gy a
-# weight gradient takes: the apply launch itself signals the event (ebsdvae_fork_arm /
-# ebsdvae_fork_wait), so no record packet sits between the apply and the input-gradient conv.
-_KFORK = os.environ.get("EBSDVAE_KFORK", "1") != "0"
-
-
-def fork_arm(device) -> bool:
-    """Arm a kernel-attached fork for the next InstanceNorm-backward apply on the current
-    stream.  Returns the token to pass to the weight gradient that consumes that apply's gy
-    (conv_wgrad(..., fork=...)); False (nothing armed) when the weight gradients will not go
-    to the side stream.  The armed state lives in the library per host thread: a later arm
-    replaces it, and only a conv_wgrad holding the token waits on it."""
-    if _KFORK and _LIGHT_EVENTS and _side_stream(device) is not None \
-            and not torch.cuda.is_current_stream_capturing():
-        N.call("ebsdvae_fork_arm", N.stream())
-        return True
-    return False
-
-
-def _side_use(device, *tensors, fork=False):
-    """Fork the side stream from the current stream and keep `tensors` alive until the join.
-    fork: fork_arm()'s token -- the side stream waits for the armed apply launch only (the
-    last main-stream work the caller's inputs depend on) instead of an event recorded now."""
-    key = _dev_key(device)
-    side = side_stream(device)
-    cur = torch.cuda.current_stream(device)
-    if fork:
-        N.call("ebsdvae_fork_wait", side.cuda_stream, cur.cuda_stream)
-    else:
-        stream_wait(side, cur)
-    keep = _KEEP.get(key)
-    if keep is None:
-        keep = _KEEP[key] = []
-    keep.extend(t for t in tensors if t is not None)
-    return side
-
-
-def _side_pending(device) -> bool:
-    return _KEEP.get(_dev_key(device)) is not None
-
-
-def _join_side(device):
-    """The current stream waits for the side stream's work so far; the buffers it used are
-    released (any later use of them is ordered behind this wait)."""
-    key = _dev_key(device)
-    if _KEEP.get(key) is not None:   # only a side stream that took work since the last join
-        stream_wait(torch.cuda.current_stream(device), _SIDE[key])
-        _KEEP[key] = None
-
-
-@contextlib.contextmanager
-def deferred_side_join(device):
-    """Batched reductions inside the block leave their results on the side stream; the
-    current stream joins it once, when the block exits."""
-    global _DEFER
-    _DEFER += 1
-    try:
-        yield
-    finally:
-        _DEFER -= 1
-        _join_side(device)
-
-
+# ------------------------------------------- reduce queue (the side stream: latice/side.py)
 # EBSDVAE_FINAL_REDUCE_SIDE=1: the encoder's last reduction batch on the side stream as through
 # round 6's middle (A/B)
 _ON_MAIN_FINAL = os.environ.get("EBSDVAE_FINAL_REDUCE_SIDE", "0") in ("", "0")
@@ -841,20 +673,14 @@ def _flush_reduces(q, on_main: bool = False):
     if not q:
         return
     dev = q[0][0].device
-    if on_main and _ON_MAIN_FINAL and _side_pending(dev):
-        _join_side(dev)   # the weight gradients' partials are complete once the side stream is
-    side = side_stream(dev) if _side_pending(dev) else None
-    if side is not None:
-        # behind the weight gradients on the side stream; partials made on the current
-        # stream (the fused network-end passes) are ordered by a fork -- only then, so a
-        # batch of side-stream partials does not wait for the current stream
-        mine = [t for e in q if not e[8] for t in e[:2]]
-        if mine:
-            _side_use(dev, *mine)
-        ctx = torch.cuda.stream(side)
-    else:
-        ctx = contextlib.nullcontext()
-    with ctx:
+    if on_main and _ON_MAIN_FINAL:
+        side.join(dev)   # the weight gradients' partials are complete once the side stream is
+    # behind the weight gradients on the side stream while it has any; partials made on the
+    # current stream (the fused network-end passes) are ordered by a fork -- only then, so a
+    # batch of side-stream partials does not wait for the current stream
+    live = side.pending(dev)
+    mine = [t for e in q if not e[8] for t in e[:2]]
+    with side.run(dev, *mine, when=live, resume=live and not mine) as keep:
         for i in range(0, len(q), N.MAX_WGRAD_BATCH):
             chunk = q[i:i + N.MAX_WGRAD_BATCH]
             descs = (N.WgradReduceDesc * len(chunk))(*[
@@ -864,10 +690,9 @@ def _flush_reduces(q, on_main: bool = False):
             work = _f64(nbytes // 8, device=dev)
             N.call("ebsdvae_wgrad_reduce_batch", ctypes.addressof(descs), len(chunk),
                    work.data_ptr(), N.stream())
-            if side is not None:
-                _KEEP[_dev_key(dev)].append(work)
-    if side is not None and not _DEFER:
-        _join_side(dev)
+            keep(work)
+    if live and not side.join_deferred():
+        side.join(dev)
 
 
 def _reduce_slices(wpart, bpart, S_, cin, cout, kind, dw, db, on_side=False):
@@ -875,7 +700,7 @@ def _reduce_slices(wpart, bpart, S_, cin, cout, kind, dw, db, on_side=False):
     e = (wpart, bpart, S_, cin, cout, kind, dw, db, on_side)
     if _RQ is not None:
         _RQ.append(e)
-    elif _side_pending(wpart.device):
+    elif side.pending(wpart.device):
         _flush_reduces([e])   # on the side stream, then joined
     else:
         nbytes = N.call("ebsdvae_wgrad_reduce_work", S_, cin, cout)
@@ -1002,21 +827,17 @@ def conv_wgrad(src, src_stats, src_mode, gy, cin, cout, kind, dw, db, normalized
                fork=False):
     """normalized: src is a normalised activation (default: the NORM modes); the split-fp16
     weight gradient (f16x3, gy with per-tile maxima) scales only gy, so it needs one.
-    Runs on the side stream (see _side_stream); dw/db are written by the slice reduction on
-    the caller's stream."""
-    side = _side_stream(gy.device)
-    if side is None:
-        return _conv_wgrad(src, src_stats, src_mode, gy, cin, cout, kind, dw, db, normalized)
-    side = _side_use(gy.device, src, src_stats, gy, getattr(gy, "ev_gmax", None), fork=fork)
-    with torch.cuda.stream(side):
-        wpart, bpart, S_ = _conv_wgrad(src, src_stats, src_mode, gy, cin, cout, kind, dw, db,
-                                       normalized, reduce=False)
-    _KEEP[_dev_key(gy.device)].extend((wpart, bpart))
-    _reduce_slices(wpart, bpart, S_, cin, cout, kind, dw, db, on_side=True)
+    Runs on the side stream where that takes work (side.run; fork: a fork_arm() token); the
+    slice reduction that writes dw/db is queued or issued from the caller's stream."""
+    gmax = getattr(gy, "ev_gmax", None)
+    with side.run(gy.device, src, src_stats, gy, gmax, fork=fork) as keep:
+        wpart, bpart, S_ = _conv_wgrad(src, src_stats, src_mode, gy, cin, cout, normalized)
+        on_side = keep(wpart, bpart)
+    _reduce_slices(wpart, bpart, S_, cin, cout, kind, dw, db, on_side=on_side)
 
 
-def _conv_wgrad(src, src_stats, src_mode, gy, cin, cout, kind, dw, db, normalized=None,
-                reduce=True):
+def _conv_wgrad(src, src_stats, src_mode, gy, cin, cout, normalized=None):
+    """The weight gradient's slice partials (wpart, bpart, their count) on the current stream."""
     B, H, W, _ = gy.shape if gy.dim() == 4 else (*gy.shape, 1)
     if normalized is None:
         normalized = src_mode in (ACT_NORM, ACT_NORM_UP)
@@ -1033,10 +854,7 @@ def _conv_wgrad(src, src_stats, src_mode, gy, cin, cout, kind, dw, db, normalize
                     N.ptr(gmax), gmax.shape[1], N.ptr(wpart), N.ptr(bpart), B, H, W, cin, cout,
                     N.stream(), tag=f"wgrad {cin:3d}->{cout:3d} @{H:3d} m{src_mode} f16",
                     pieces=PIECES_F16, nbytes=nbw)
-            if not reduce:
-                return wpart, bpart, S_
-            _reduce_slices(wpart, bpart, S_, cin, cout, kind, dw, db)
-            return
+            return wpart, bpart, S_
     np_ = _PIECES[_PRECISION]
     S_ = N.call("ebsdvae_conv3x3_wgrad_split_slices", B, H, W, cin, cout, np_) if np_ else -1
     if S_ <= 0:
@@ -1056,9 +874,7 @@ def _conv_wgrad(src, src_stats, src_mode, gy, cin, cout, kind, dw, db, normalize
     else:
         _launch("conv3x3_wgrad", conv_flops(B, H, W, cin, cout), N.call, "ebsdvae_conv3x3_wgrad",
                 *args, s, tag=tag, nbytes=nbw)
-    if not reduce:
-        return wpart, bpart, S_
-    _reduce_slices(wpart, bpart, S_, cin, cout, kind, dw, db)
+    return wpart, bpart, S_
 
 
 def conv_dgrad(gy, layer: ConvLayer, w, prev=None, wd=None, sum_up=False, ypool=None):
@@ -1402,18 +1218,12 @@ def heads_backward(plan: Plan, g_dec, g_z, g_mu, g_std, flat, std, z, eps, param
     out = {n: _grad_buf(grads, n, params[n]) for n in HEAD_NAMES}
     # the heads' weight gradients are off the critical path (g_enc is all the encoder
     # backward needs): on the side stream inside deferred_side_join() (the trainer's step)
-    side = _side_stream(g_dec.device) if _DEFER else None
-    ctx = contextlib.nullcontext()
-    if side is not None:
-        side = _side_use(g_dec.device, flat, z, gs)
-        ctx = torch.cuda.stream(side)
-    with ctx:
+    with side.run(g_dec.device, flat, z, gs, when=side.join_deferred()) as keep:
         nbytes = N.call("ebsdvae_heads_wgrad_work", B, F, L)
         work = _scratch(nbytes // 4, device=g_dec.device)
         N.call("ebsdvae_heads_wgrad", N.ptr(flat), N.ptr(z), N.ptr(gs),
                *[N.ptr(out[n]) for n in HEAD_NAMES], N.ptr(work), B, F, L, N.stream())
-    if side is not None:
-        _KEEP[_dev_key(g_dec.device)].append(work)
+        keep(work)
     return g_enc, out
 
 
@@ -1514,13 +1324,8 @@ def loss_forward(x_hat, x, z, mu, std, kl_lambda: float):
     elbo, kl, recon = _empty(B, like=x_hat), _empty(B, like=x_hat), _empty(B, like=x_hat)
     loss, kl_loss, recon_loss = (_scratch(device=x_hat.device)
                                  for _ in range(3))
-    side = _side_stream(x_hat.device) if _DEFER else None
-    ctx = contextlib.nullcontext()
-    if side is not None:
-        side = _side_use(x_hat.device, x_hat, x, z, mu, std, elbo, kl, recon, loss, kl_loss,
-                         recon_loss)
-        ctx = torch.cuda.stream(side)
-    with ctx:
+    with side.run(x_hat.device, x_hat, x, z, mu, std, elbo, kl, recon, loss, kl_loss, recon_loss,
+                  when=side.join_deferred()):
         N.call("ebsdvae_vae_loss_fwd", N.ptr(x_hat), N.ptr(x), N.ptr(z), N.ptr(mu), N.ptr(std),
                float(kl_lambda), N.ptr(elbo), N.ptr(kl), N.ptr(recon), N.ptr(loss), N.ptr(kl_loss),
                N.ptr(recon_loss), B, P, L, N.stream())
@@ -1533,12 +1338,8 @@ def loss_forward_parts(end: NetEnd, z, mu, std, kl_lambda: float, P: int):
     elbo, kl, recon = _empty(B, like=z), _empty(B, like=z), _empty(B, like=z)
     loss, kl_loss, recon_loss = (_scratch(device=z.device)
                                  for _ in range(3))
-    side = _side_stream(z.device) if _DEFER else None
-    ctx = contextlib.nullcontext()
-    if side is not None:
-        side = _side_use(z.device, end.bce, z, mu, std, elbo, kl, recon, loss, kl_loss, recon_loss)
-        ctx = torch.cuda.stream(side)
-    with ctx:
+    with side.run(z.device, end.bce, z, mu, std, elbo, kl, recon, loss, kl_loss, recon_loss,
+                  when=side.join_deferred()):
         N.call("ebsdvae_vae_loss_fwd_parts", N.ptr(end.bce), end.tiles, N.ptr(z), N.ptr(mu),
                N.ptr(std), float(kl_lambda), N.ptr(elbo), N.ptr(kl), N.ptr(recon), N.ptr(loss),
                N.ptr(kl_loss), N.ptr(recon_loss), B, P, L, N.stream())

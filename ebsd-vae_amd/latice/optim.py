@@ -3,7 +3,7 @@
 Drop-in for the reference's optimiser factories (latice/lightning_module.py:26-28:
 `Adam(lr=1e-4, weight_decay=0, amsgrad=True)`; Hydra default
 conf/lightning_module/default.yaml:10-13: `Adam(lr=1e-4)`).  One ebsdvae_adam launch per
-parameter tensor (or per flat buffer, see trainer.FlatParams), state kept on the device,
+parameter tensor (trainer.VAETrainer.optimizer_step: one over its flat buffer), state kept on the device,
 bias corrections computed on the device from a device step counter.
 """
 from __future__ import annotations

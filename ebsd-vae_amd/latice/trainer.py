@@ -24,6 +24,7 @@ import torch.distributed as dist
 
 from . import _native as N
 from . import engine as E
+from . import side
 from .functional import dec_param_names, enc_param_names
 
 
@@ -154,19 +155,11 @@ class VAETrainer:
             self.gflat.fill_(float("nan"))
         # one launch packs every conv weight of the step, and the reparameterisation noise is
         # drawn: both on the side stream, beside the first conv (which reads its weight
-        # unpacked); the current stream waits for them before the first packed layer
-        side = E.side_stream(x.device) if E.side_streams_enabled() else None
-        if side is not None:
-            main = torch.cuda.current_stream(x.device)
-            E.stream_wait(side, main)
-            with torch.cuda.stream(side):
-                packs = self.packset.refresh()
-                eps = self._noise(x.shape[0]) if eps is None else eps
-            ready = lambda: E.stream_wait(main, side)   # noqa: E731
-        else:
+        # unpacked), joined before the first packed layer (both write the trainer's own buffers)
+        with side.run(x.device):
             packs = self.packset.refresh()
             eps = self._noise(x.shape[0]) if eps is None else eps
-            ready = None
+        ready = (lambda: side.join(x.device)) if side.pending(x.device) else None
         enc, se = E.encoder_forward(plan, x, P, packs=packs, packs_ready=ready)
         flat, mu, std, z, dec_in = E.heads_forward(plan, enc, P, eps)
         fused_end = E.net_end_ok(plan)
@@ -226,12 +219,7 @@ class VAETrainer:
         """Start a bucket's all-reduce behind everything issued so far on both streams: the
         side stream carries the weight gradients (and their reductions), the current stream
         the rest (heads backward, first-layer fused weight gradient)."""
-        if not E.side_streams_enabled():
-            self.reducer.start(bucket)
-            return
-        side = E.side_stream(device)
-        E.stream_wait(side, torch.cuda.current_stream(device))
-        with torch.cuda.stream(side):
+        with side.run(device):
             self.reducer.start(bucket)
 
     def optimizer_step(self):

@@ -26,6 +26,7 @@ import torch
 from pinned import check_grads, fixture
 from latice import engine as E
 from latice import model as M
+from latice import side as S
 from latice.model import VariationalAutoEncoderRawData
 from latice.trainer import VAETrainer
 
@@ -58,7 +59,8 @@ def test_schedule_switch_gives_bitwise_equal_gradients(cuda, monkeypatch, attr, 
     f, m = _model(cuda)
     tr0, _ = _grad(m, f, cuda, copies)
     g0 = tr0.gflat.clone()
-    monkeypatch.setattr(E, attr, False)
+    # patched in the module that reads it (setattr raises where the name does not exist)
+    monkeypatch.setattr(E if attr == "_ON_MAIN_FINAL" else S, attr, False)
     tr1, _ = _grad(m, f, cuda, copies)
     assert torch.equal(tr1.gflat, g0), f"{attr}=0 changed the gradient"
 
@@ -72,7 +74,7 @@ def test_graph_side_switch_gives_bitwise_equal_steps(cuda, monkeypatch):
     flats = []
     for side in (True, False):
         _, m = _model(cuda)
-        monkeypatch.setattr(E, "_GRAPH_SIDE", side)
+        monkeypatch.setattr(S, "_GRAPH_SIDE", side)
         tr = VAETrainer(m, kl_lambda=float(f["kl_lambda"]), seed=5)
         tr.capture(x, warmup=1)
         tr.replay()
