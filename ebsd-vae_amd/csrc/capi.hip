@@ -75,8 +75,9 @@ int ring_event(ebsdvae_stream_t signaler, int kind, hipEvent_t* out) {
       return 2;
     }
     bool ok = true;
-    const char* ds = getenv("EBSDVAE_FORK_DEVICE_SCOPE");
-    const unsigned f0 = hipEventDisableTiming | ((ds && ds[0] == '1') ? hipEventReleaseToDevice : 0u);
+    // off by default; read when a device's ring is made
+    const bool dscope = evh::env_flag("EBSDVAE_FORK_DEVICE_SCOPE", false);
+    const unsigned f0 = hipEventDisableTiming | (dscope ? hipEventReleaseToDevice : 0u);
     for (int i = 0; i < kRing && ok; ++i)
       ok = hipEventCreateWithFlags(&g_ring[kind][dev][i], kind == 0 ? f0 : hipEventDefault) == hipSuccess;
     (void)hipSetDevice(cur);

@@ -10,6 +10,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
+#include <type_traits>
 
 #define EV_DEVINL __device__ __forceinline__
 // device lambdas that must inline (a call spills the whole register state)
@@ -206,6 +208,33 @@ hipEvent_t take_fork_event();
 // compute units a stream may run on: the count registered by ebsdvae_stream_create_cus for a
 // CU-masked stream, else 0 (the device's; the persistent kernels size their grids by it)
 int stream_cus(hipStream_t s);
+
+// The library's run-time switches (EBSDVAE_* environment variables).  A site that reads one
+// keeps the answer in a function-local static, so each switch is read once per process.
+// A flag that is on by default goes off only for a value starting with '0'; one that is off by
+// default goes on only for a value starting with '1'.
+inline bool env_flag(const char* name, bool def) {
+  const char* e = getenv(name);
+  return e ? (def ? e[0] != '0' : e[0] == '1') : def;
+}
+// An integer in [lo, hi]; unset or out of range gives def.
+inline int env_int(const char* name, int def, int lo, int hi) {
+  const char* e = getenv(name);
+  const int t = e ? atoi(e) : def;
+  return (t >= lo && t <= hi) ? t : def;
+}
+
+// Run-time value -> compile-time constant: calls f(std::integral_constant<int, V>) for the
+// first V of the list equal to v, and for the last one when none is (the "default:" case).
+template <int V0, int... Vs, class F>
+inline void with_const(int v, F&& f) {
+  if constexpr (sizeof...(Vs) == 0) {
+    f(std::integral_constant<int, V0>());
+  } else {
+    if (v == V0) f(std::integral_constant<int, V0>());
+    else with_const<Vs...>(v, f);
+  }
+}
 }  // namespace evh
 
 // a spatial extent the shape queries accept (H * W and its multiples stay inside int)

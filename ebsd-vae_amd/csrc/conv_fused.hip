@@ -25,14 +25,13 @@
 // tile the block stages the 10 x 10 halo of gy and of the activation into LDS as fp16 pieces
 // (pixel-major records, 96-B rows), double-buffered: four staging waves transform, split and
 // write tile t+1 while their registers refill with tile t+2's loads, beside eight MFMA waves on
-// tile t (one barrier per tile; DW_NOSPEC: the round-5 first form, where the MFMA waves stage
-// between their taps).  MFMA waves:
+// tile t (one barrier per tile).  MFMA waves:
 //   weight gradient: wave w owns the (co 16 x ci 16) block (w & 1, (w >> 1) & 1) for the tile's
 //     pixels 32 (w >> 2) .. +31 (one k-step of v_mfma_f32_16x16x32_f16 per tap; the two pixel
 //     halves are folded at the end), operands by transposed LDS reads (ds_read_b64_tr_b16);
 //   input gradient: wave w owns output pixels 16 (w & 3) .. +15 x ci 16 (w >> 2): per tap one
 //     K = 32 (all gy channels) MFMA, A = the gy halo shifted by the tap (ds_read_b128), B = the
-//     weight pack (resident in LDS; DW_NOSPEC: in registers).
+//     weight pack (resident in LDS).
 // Each tap's LDS operands are read during the previous tap's MFMAs (one tap ahead).
 // Both run the split-fp16 products a1 b0 + a0 b1 + a0 b0 (f16x3).  The gy operand carries one
 // power-of-two scale per slice (from the applies' per-tile maxima, as the weight gradient's), the
@@ -54,7 +53,7 @@ constexpr int DW_IMG = 2 * DW_PIECE;               // two pieces
 constexpr int DW_BUF = 2 * DW_IMG;                 // gy image + activation image
 constexpr int DW_WPACK = 4 * 10 * 2 * DW_C * 8 * 2;  // the dgrad pack (4 chunks x 10 taps x 2 pieces)
 constexpr int DW_NTH = 512;       // the MFMA waves
-constexpr int DW_NTH_SPEC = 768;  // SPEC: + 4 staging waves
+constexpr int DW_NTH_BLOCK = 768; // + 4 staging waves
 constexpr int DW_ITEMS = DW_HALO * (DW_C / 4);     // float4 items of one halo tensor
 constexpr size_t DW_LDS = (size_t)DW_WPACK + 2 * (size_t)DW_BUF + 4096;
 
@@ -101,12 +100,12 @@ struct DwGeom {
 
 // UPS: the source is at H/2 x W/2 (decoder.13: ACT_NORM_UP, the input gradient summed over 2x2
 // windows, FP_UPSUM); else the same resolution (encoder.1: ACT_NORM, P_ID)
-// SPEC (round 5): 4 more waves (768 threads) do all the staging -- item loads, normalisation, fp16
-// split, LDS stores, bias sums -- so the 8 MFMA waves run their taps without it and the staging
-// VALU can issue beside their MFMAs on the same SIMDs; the input-gradient weights are then read
-// from LDS per tap (the 168-VGPR budget of three waves per SIMD has no room for them)
-template <bool UPS, bool SPEC>
-__global__ __launch_bounds__(SPEC ? DW_NTH_SPEC : DW_NTH, 1) void dwgrad_fused_kernel(
+// Staging waves (round 5): 4 more waves (768 threads) do all the staging -- item loads,
+// normalisation, fp16 split, LDS stores, bias sums -- so the 8 MFMA waves run their taps without it
+// and the staging VALU can issue beside their MFMAs on the same SIMDs; the input-gradient weights
+// are read from LDS per tap (the 168-VGPR budget of three waves per SIMD has no room for them)
+template <bool UPS>
+__global__ __launch_bounds__(DW_NTH_BLOCK, 1) void dwgrad_fused_kernel(
     const float* __restrict__ gy, const float* __restrict__ gmax, int gmT,
     const char* __restrict__ wpack, const float* __restrict__ yprev, const float2* __restrict__ stp,
     float* __restrict__ hout, double2* __restrict__ ipart, float* __restrict__ wpart,
@@ -122,10 +121,10 @@ __global__ __launch_bounds__(SPEC ? DW_NTH_SPEC : DW_NTH, 1) void dwgrad_fused_k
   const int Hs = UPS ? H / 2 : H, Ws = UPS ? W / 2 : W;
   const int per_img = g.ntx * g.ntx;
   constexpr int C = DW_C;
-  constexpr int NTH = SPEC ? DW_NTH_SPEC : DW_NTH;   // threads
-  constexpr int NST = SPEC ? NTH - DW_NTH : DW_NTH;  // staging threads
+  constexpr int NTH = DW_NTH_BLOCK;                  // threads
+  constexpr int NST = NTH - DW_NTH;                  // staging threads
   constexpr int KS = (DW_ITEMS + NST - 1) / NST;     // items per staging thread per tensor
-  const bool stager = SPEC && wave >= DW_NTH / 64;   // wave-uniform
+  const bool stager = wave >= DW_NTH / 64;           // wave-uniform
 
   // ---- the dgrad weight pack -> LDS (resident), its layer shift from the trailer
   for (int i = tid; i < DW_WPACK / 16; i += NTH)
@@ -140,7 +139,7 @@ __global__ __launch_bounds__(SPEC ? DW_NTH_SPEC : DW_NTH, 1) void dwgrad_fused_k
   // ---- item geometry (tile-invariant): item k of this thread is halo pixel hp = (tid + 512 k)
   // / 8 of the tile (row hr, column hc, -1 .. 8), channels 4 qd .. 4 qd + 3.  The same items
   // stage gy (this block's output gradient) and the activation source.
-  const int sid = SPEC ? tid - DW_NTH : tid;   // staging thread index (SPEC: waves 8-11)
+  const int sid = tid - DW_NTH;   // staging thread index (waves 8-11)
   const int qd = sid & 7;
   int hrc[KS], ldo[KS], gyo[KS], sro[KS];
   bool live[KS], inner[KS];
@@ -168,8 +167,7 @@ __global__ __launch_bounds__(SPEC ? DW_NTH_SPEC : DW_NTH, 1) void dwgrad_fused_k
     x0 = (rr & (g.ntx - 1)) * DW_TS;
   };
   // registers: gy and activation items of the loading tile (l*) and stats of the staging tile (s*)
-  // two register slots (SPEC staging waves: tile u's loads are issued two tiles before it is
-  // staged; the MFMA waves' in-tap staging uses slot 0 only)
+  // two register slots (tile u's loads are issued two tiles before it is staged)
   float4 rg[2][KS], ra[2][KS];
   float2 fl[2][4], fs[4];   // {rstd, -mean*rstd} of the item channels, loading / staging tile image
   int lb[2] = {0, 0}, ly[2] = {0, 0}, lx[2] = {0, 0}, sy = 0, sx = 0;
@@ -335,12 +333,9 @@ __global__ __launch_bounds__(SPEC ? DW_NTH_SPEC : DW_NTH, 1) void dwgrad_fused_k
   // ---- prologue: tile t_beg staged into set 0, tile t_beg + 1 (clamped) in the registers
   const std::integral_constant<int, 0> S0;
   const std::integral_constant<int, 1> S1;
-  if (stager) {             // SPEC: tiles t_beg, t_beg + 1 into slots 0, 1
+  if (stager) {             // tiles t_beg, t_beg + 1 into slots 0, 1
     issue(t_beg, S0);
     issue(min(t_beg + 1, t_end - 1), S1);
-  } else if (!SPEC) {
-    issue(t_beg, S0);
-    shift(S0);
   }
   __syncthreads();   // the weight pack is in LDS before anyone reads it (and before set 0 is read)
   if (stager) {
@@ -349,25 +344,11 @@ __global__ __launch_bounds__(SPEC ? DW_NTH_SPEC : DW_NTH, 1) void dwgrad_fused_k
     for (int k = 0; k < KS; ++k) stage(k, lbuf, S0);
     bs[0] += (double)tb.x; bs[1] += (double)tb.y; bs[2] += (double)tb.z; bs[3] += (double)tb.w;
     issue(min(t_beg + 2, t_end - 1), S0);
-  } else if (!SPEC) {
-#pragma unroll
-    for (int k = 0; k < KS; ++k) stage(k, lbuf, S0);
-    bs[0] += (double)tb.x; bs[1] += (double)tb.y; bs[2] += (double)tb.z; bs[3] += (double)tb.w;
-    issue(min(t_beg + 1, t_end - 1), S0);
   }
   __syncthreads();
 
-  // the input-gradient B fragments of this lane (the pack: 9 taps x 2 pieces) stay in registers
-  // for the whole slice (72 VGPRs; read once instead of once per tile: -30 us at B = 256)
-  f16x8 dbr[9][2];
-  if constexpr (!SPEC) {
-#pragma unroll
-    for (int tap = 0; tap < 9; ++tap)
-#pragma unroll
-      for (int i = 0; i < 2; ++i) dbr[tap][i] = dw_frag(lw + ((((gq * 10 + tap) * 2 + i) * C) + eci) * 16);
-  }
   if (stager) {
-    // SPEC staging waves (their own loop, so their registers are not live beside the MFMA
+    // staging waves (their own loop, so their registers are not live beside the MFMA
     // waves' accumulators): tile t+1 into the other set, then its registers refill with t+2
     // tile t+1 is in slot (t + 1 - t_beg) & 1; its slot refills with tile t+3
     auto stager_tile = [&](int t, auto sl_c) EV_LAMBDA_INLINE {
@@ -391,13 +372,8 @@ __global__ __launch_bounds__(SPEC ? DW_NTH_SPEC : DW_NTH, 1) void dwgrad_fused_k
     const int cur = (t - t_beg) & 1;
     const char* gimgp = lbuf + cur * DW_BUF;
     const char* aimgp = gimgp + DW_IMG;
-    char* nbuf = lbuf + (1 - cur) * DW_BUF;
     pre_load(t);
     if (t > t_beg && tid < C) combine(t - 1);   // the previous tile's slot sums (behind its barrier)
-    if constexpr (!SPEC) {
-      shift(S0);
-      tb = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
     // weight-gradient A fragments (gy, k = this wave's 32 pixels): one read per piece
     f16x8 wa[2];
 #pragma unroll
@@ -425,42 +401,24 @@ __global__ __launch_bounds__(SPEC ? DW_NTH_SPEC : DW_NTH, 1) void dwgrad_fused_k
       __builtin_amdgcn_sched_barrier(0);   // issued ahead of this tap's MFMAs
       const f16x8* wb = wbc;
       const f16x8* da = dac;
-      f16x8 dbt[2];
-      if constexpr (SPEC) {
+      f16x8 db[2];   // the input-gradient B fragments of this tap, from the resident pack
 #pragma unroll
-        for (int i = 0; i < 2; ++i) dbt[i] = dw_frag(lw + ((((gq * 10 + tap) * 2 + i) * C) + eci) * 16);
-      }
-      const f16x8* db = SPEC ? dbt : dbr[tap];
+      for (int i = 0; i < 2; ++i) db[i] = dw_frag(lw + ((((gq * 10 + tap) * 2 + i) * C) + eci) * 16);
       accw[tap] = dw_mfma(wa[1], wb[0], accw[tap]);
       accw[tap] = dw_mfma(wa[0], wb[1], accw[tap]);
       accw[tap] = dw_mfma(wa[0], wb[0], accw[tap]);
       accd = dw_mfma(da[1], db[0], accd);
       accd = dw_mfma(da[0], db[1], accd);
       accd = dw_mfma(da[0], db[0], accd);
-      // staging of tile t+1 between the taps (item k at tap 2 k + 1), then its register
-      // refill is tile t+2's load (issued once, after the last item)
-      if constexpr (!SPEC) {
-        dw_for<KS>([&](auto k_c) EV_LAMBDA_INLINE {
-          constexpr int k = decltype(k_c)::value;
-          if constexpr (tap == 2 * k + 1) stage(k, nbuf, S0);
-        });
-        if constexpr (tap == 2 * KS) issue(min(t + 2, t_end - 1), S0);
-      }
       if constexpr (tap < 8) {
 #pragma unroll
         for (int i = 0; i < 2; ++i) { wbc[i] = wbn[i]; dac[i] = dan[i]; }
       }
     });
-    // branch-free (the surplus copy of the last tile is weighted 0), and 24 wait states before
-    // the epilogue reads accd: with a conditional block here, hipcc (ROCm 7.2) put the epilogue's
-    // first VALU read of the last MFMA's result right behind the branch on the skipping path,
-    // without the wait states an MFMA result needs (wrong input gradients on every slice's last
-    // tile, tools/debug/dw_ups.py)
-    if constexpr (!SPEC) {
-      const float keep = (t + 1 < t_end) ? 1.f : 0.f;
-      bs[0] += (double)(tb.x * keep); bs[1] += (double)(tb.y * keep);
-      bs[2] += (double)(tb.z * keep); bs[3] += (double)(tb.w * keep);
-    }
+    // 24 wait states before the epilogue reads accd: with a conditional block here, hipcc
+    // (ROCm 7.2) put the epilogue's first VALU read of the last MFMA's result right behind the
+    // branch on the skipping path, without the wait states an MFMA result needs (wrong input
+    // gradients on every slice's last tile, tools/debug/dw_ups.py)
     asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 7" ::: "memory");
     epilogue(t);
     accd = dw_f32x4{0.f, 0.f, 0.f, 0.f};
@@ -471,7 +429,7 @@ __global__ __launch_bounds__(SPEC ? DW_NTH_SPEC : DW_NTH, 1) void dwgrad_fused_k
 
   // ---- weight-gradient partials: fold the two pixel halves (waves 4-7 into 0-3) through LDS
   float* xs = reinterpret_cast<float*>(lbuf);   // LDS sets are free after the last barrier
-  if (wks == 1) {   // waves 4-7 (SPEC staging waves: wks == 2)
+  if (wks == 1) {   // waves 4-7 (staging waves: wks == 2)
 #pragma unroll
     for (int t = 0; t < 9; ++t)
 #pragma unroll
@@ -545,18 +503,13 @@ extern "C" int ebsdvae_conv3x3_dwgrad_f16(const float* gy, const float* gmax, in
   EV_REQUIRE(cin == DW_C && cout == DW_C && dw_geom(B, H, W, &g),
              "conv3x3_dwgrad_f16: unsupported shape B=%d H=%d W=%d cin=%d cout=%d", B, H, W, cin, cout);
   hipStream_t s = (hipStream_t)stream;
-  auto launch = [&](auto kern, int nth) {
+  auto launch = [&](auto kern) {
     (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)DW_LDS);
-    hipLaunchKernelGGL(kern, dim3(g.slices), dim3(nth), DW_LDS, s, gy, gmax, gm_tiles,
+    hipLaunchKernelGGL(kern, dim3(g.slices), dim3(DW_NTH_BLOCK), DW_LDS, s, gy, gmax, gm_tiles,
                        (const char*)wpack, y_prev, (const float2*)st_prev, gin, (double2*)part, wpart,
                        bpart, B, H, W, g);
   };
-#ifdef DW_NOSPEC   // A/B: every wave stages between its taps (no staging waves)
-  if (src_mode == ACT_NORM) launch(dwgrad_fused_kernel<false, false>, DW_NTH);
-  else launch(dwgrad_fused_kernel<true, false>, DW_NTH);
-#else
-  if (src_mode == ACT_NORM) launch(dwgrad_fused_kernel<false, true>, DW_NTH_SPEC);
-  else launch(dwgrad_fused_kernel<true, true>, DW_NTH_SPEC);
-#endif
+  if (src_mode == ACT_NORM) launch(dwgrad_fused_kernel<false>);
+  else launch(dwgrad_fused_kernel<true>);
   return evh::check_launch("conv3x3_dwgrad_f16");
 }

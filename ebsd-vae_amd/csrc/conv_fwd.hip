@@ -130,10 +130,6 @@ __global__ __launch_bounds__(NWV * 64, 2) void conv3x3_big_kernel(
     for (int k = 0; k < KX; ++k) {
       const int hv = hw[k] < 0 ? 0 : hw[k];
       const int gh = hv >> 16, gw = hv & 0xffff;
-#ifdef EV_TIMING_PROBE_NOHALO   // timing experiment only: no halo traffic (wrong results)
-      raw[k][0] = make_float4(gh, gw, 1.f, 1.f);
-      continue;
-#endif
       if (POOL) {
         const float* p = sb + ((size_t)(2 * gh) * Ws + 2 * gw) * Cin + c;
         const size_t rs = (size_t)Ws * Cin;

@@ -31,16 +31,6 @@ namespace ev {
 
 static_assert(NP_F16 == EBSDVAE_PIECES_F16, "piece-format id");
 
-#ifdef EV_PIPE_TRACE   // diagnostic build only: per-wave cycle split of conv3x3_pipe_kernel
-__device__ unsigned long long ev_pipe_trace[4096 * 8 * 6];
-#define EV_T(x) unsigned long long x = __builtin_amdgcn_s_memtime()
-#define EV_TACC(acc, t0) acc += __builtin_amdgcn_s_memtime() - t0
-#else
-#define EV_T(x)
-#define EV_TACC(acc, t0)
-#endif
-
-
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
@@ -216,11 +206,7 @@ __global__ __launch_bounds__(NWV * 64, 2) void conv3x3_split_kernel(
       } else if (UPS) {
         raw[k][0] = ld4(sb + ((size_t)(gh >> 1) * Ws + (gw >> 1)) * Cin + c);
       } else {
-#ifdef EV_X_NOLOAD   // timing experiment only: no halo loads (wrong results)
-        raw[k][0] = make_float4((float)gh, (float)gw, 0.f, 1.f);
-#else
         raw[k][0] = ld4(sb + ((size_t)gh * Ws + gw) * Cin + c);
-#endif
       }
     }
     if (NORM) {
@@ -305,7 +291,6 @@ __global__ __launch_bounds__(NWV * 64, 2) void conv3x3_split_kernel(
         for (int i = 0; i < NP; ++i) b[i][nf] = lds_frag(pb + i * NT * 16);
       }
       // terms of total order < NP, smallest first
-#ifndef EV_X_NOMFMA   // timing experiment only: no MFMAs (wrong results)
 #pragma unroll
       for (int mf = 0; mf < MF; ++mf)
 #pragma unroll
@@ -319,11 +304,6 @@ __global__ __launch_bounds__(NWV * 64, 2) void conv3x3_split_kernel(
           acc[mf][nf] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0][mf], b[1][nf], acc[mf][nf], 0, 0, 0);
           acc[mf][nf] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0][mf], b[0][nf], acc[mf][nf], 0, 0, 0);
         }
-#else
-      for (int mf = 0; mf < MF; ++mf)
-        for (int nf = 0; nf < NF; ++nf)
-          for (int i = 0; i < NP; ++i) acc[mf][nf][i] += (float)a[i][mf][0] * (float)b[i][nf][1];
-#endif
     }
     if (more) store_halo(lx0 + nxt * xslab);
     __syncthreads();
@@ -337,13 +317,6 @@ __global__ __launch_bounds__(NWV * 64, 2) void conv3x3_split_kernel(
 // compiler from moving LDS / global accesses across it.
 // 1-KiB LDS-DMA pieces per wave and chunk of the pipelined kernel's weight slab
 constexpr int pipe_dma_per(int wslab, int nwv) { return (wslab / 1024 + nwv - 1) / nwv; }
-// halo items staged at k-step s of the pipelined kernel (item k goes to k-step k*5/KX, or all
-// to the last k-step when the prefetch distance is 1)
-constexpr int pipe_items_at(int s, int kx, int pd) {
-  int n = 0;
-  for (int k = 0; k < kx; ++k) n += ((pd == 2 ? (k * 5) / kx : 4) == s) ? 1 : 0;
-  return n;
-}
 
 // Workgroup barrier with no vector-memory wait (resident-weight kernels: no LDS-DMA in the loop,
 // and every register load is waited for by the compiler where it is used): lgkmcnt(0) only
@@ -404,10 +377,7 @@ EV_DEVINL void pipe_epilogue(f32x16 (&acc)[MF][NF], const float* __restrict__ bi
   // input-gradient launches (a fused IN-backward reduce or the summed upsample adjoint) pass no
   // statistics partials (spart == nullptr)
   constexpr bool FUSED = FP == P_ID || FP == P_POOL || FP == P_UP || FP == FP_UPSUM;
-#ifndef EV_EPI_OPAQUE
-#define EV_EPI_OPAQUE 1
-#endif
-  constexpr bool EPI_OPAQUE = EV_EPI_OPAQUE && FP == FP_POOLOUT;
+  constexpr bool EPI_OPAQUE = FP == FP_POOLOUT;
   if constexpr (PH == 1) {   // loads only: the offsets of the PH 0 / 2 code below
     const int nf = 0;
     const int co = co_base + l32;
@@ -642,12 +612,9 @@ EV_DEVINL void pipe_epilogue(f32x16 (&acc)[MF][NF], const float* __restrict__ bi
 // k-step, 40 VGPRs per chunk, double-buffered by chunk parity) instead of DMA-ing the 40-KiB
 // slab into LDS and reading it back: the four waves need disjoint 32-channel column blocks of
 // it, so the LDS round trip carried no reuse, and its writes and reads were half of the
-// iteration's LDS traffic (EV_WREG=0: the LDS slab, A/B)
-#ifndef EV_WREG
-#define EV_WREG 1
-#endif
+// iteration's LDS traffic
 constexpr bool pipe_wreg(int NWV, int WM, int NF, int NI, int WR) {
-  return EV_WREG && NWV == 4 && WM == 1 && NF == 1 && NI == 1 && WR == 0;
+  return NWV == 4 && WM == 1 && NF == 1 && NI == 1 && WR == 0;
 }
 
 // Persistent, software-pipelined form of conv3x3_split_kernel (same tiles, LDS layouts,
@@ -868,11 +835,7 @@ __global__ __launch_bounds__(NWV * 64, (MODE == ACT_FIRST || pipe_wreg(NWV, WM, 
     const auto rs = __builtin_amdgcn_make_buffer_rsrc((void*)(src + (size_t)b0 * Hs * Ws * Cin), 0,
                                                       NI == 1 ? img_bytes : img_bytes * min(NI, B - b0),
                                                       0x00020000);
-#ifdef EV_X_CONTIG
-    const int toff = h0 * rowb + ch * (pixP * 32);
-#else
     const int toff = (POOL ? 2 * h0 : (UPS ? (h0 >> 1) : h0)) * rowb + ch * XCK * 4;
-#endif
 #pragma unroll
     for (int k = 0; k < KX; ++k) {
       const int vo = boff[k] + toff;
@@ -922,18 +885,6 @@ __global__ __launch_bounds__(NWV * 64, (MODE == ACT_FIRST || pipe_wreg(NWV, WM, 
       float nb[9];
 #pragma unroll
       for (int t = 0; t < 9; ++t) nb[t] = xw[(t / 3) * (W + 2) + t % 3];
-#ifdef EV_FIRST_PK   // A/B: the channel pairs on v_pk_fma_f32 (first_conv_px2)
-      pkf2 wa[9], wb[9];
-#pragma unroll
-      for (int t = 0; t < 9; ++t) {
-        wa[t] = pk2(wq[t].x, wq[t].y);
-        wb[t] = pk2(wq[t].z, wq[t].w);
-      }
-      const pkf2 ya = first_conv_px2(nb, wa, pk2(wq[9].x, wq[9].y));
-      const pkf2 yb = first_conv_px2(nb, wb, pk2(wq[9].z, wq[9].w));
-      v = make_float4(normact_fs(ya.x, fs[0]), normact_fs(ya.y, fs[1]), normact_fs(yb.x, fs[2]),
-                      normact_fs(yb.y, fs[3]));
-#else
       // scalar v_fma_f32 chains (a packed fma beside MFMAs costs more issue than two scalar
       // ones, MI355X_MICROARCH.md); each lane of first_conv_px2 is exactly this chain
       float wc[4][9];
@@ -945,7 +896,6 @@ __global__ __launch_bounds__(NWV * 64, (MODE == ACT_FIRST || pipe_wreg(NWV, WM, 
                       normact_fs(first_conv_px(nb, wc[1], wq[9].y), fs[1]),
                       normact_fs(first_conv_px(nb, wc[2], wq[9].z), fs[2]),
                       normact_fs(first_conv_px(nb, wc[3], wq[9].w), fs[3]));
-#endif
     } else {
       v = stage_value(slot_c, k, fs);
     }
@@ -1039,11 +989,7 @@ __global__ __launch_bounds__(NWV * 64, (MODE == ACT_FIRST || pipe_wreg(NWV, WM, 
   const int ncol = wn * NF * 32 + l32;
   // fused IN-backward reduce of one fragment column: the tile's y_prev values are loaded at the
   // start of its last iteration (pipe_epilogue PH 1) and consumed by its epilogue (PH 2)
-#ifdef EV_PIPE_NOPREF   // A/B: load them inside the epilogue
-  constexpr bool PREF = false;
-#else
   constexpr bool PREF = pipe_prefetch_ok<MF, NF, FP>() && NI == 1;
-#endif
   float pv[pipe_prefetch_n<MF, NF, FP>()];
   auto epi_prefetch = [&](int it) EV_LAMBDA_INLINE {
     int b0, h0, ch;
@@ -1061,27 +1007,17 @@ __global__ __launch_bounds__(NWV * 64, (MODE == ACT_FIRST || pipe_wreg(NWV, WM, 
       sc = ldexpf(1.f, -wshift);
       if constexpr (GS) sc = ldexpf(sc, -gshift(min(b0 + im, B - 1)));
     }
-#ifdef EV_PIPE_NOEPI   // timing experiment only: no epilogue (no output, wrong results)
-    if (sc == 12345.f)
-#else
     if (NI == 1 || b0 + im < B)
-#endif
       pipe_epilogue<MF, NF, FP, NT, PREF ? 2 : 0>(ea, bias, y, spart, H, W, b0 + im, h0, wpx0, mfs,
                                                   (h0 * W + wm * MW - im * tpx) / 64, wn * NF * 32, hk,
                                                   l32, yprev, stprev, ipart, ypool, sc, pv);
   };
 
-#ifdef EV_PIPE_TRACE
-  unsigned long long tr_issue = 0, tr_k = 0, tr_bar = 0, tr_epi = 0;
-  const unsigned long long tr_start = __builtin_amdgcn_s_memtime();
-  const unsigned long long tr_rstart = __builtin_amdgcn_s_memrealtime();
-#endif
   // one pipelined iteration; P = it & 1 selects the LDS buffers and register slots statically
   auto body = [&](int it, auto P_c) EV_LAMBDA_INLINE {
     constexpr int P = decltype(P_c)::value;
     constexpr int SL_LD = PD == 2 ? P : 0;        // slot receiving it+PD
     constexpr int SL_ST = PD == 2 ? 1 - P : 0;    // slot holding it+1
-    EV_T(tb0);
     // unconditional issue (indices clamped at the end: the surplus loads land in buffers
     // nobody reads), so every iteration has the same vector-memory op count
     const int it1 = min(it + 1, nit - 1), itp = min(it + PD, nit - 1);
@@ -1090,13 +1026,9 @@ __global__ __launch_bounds__(NWV * 64, (MODE == ACT_FIRST || pipe_wreg(NWV, WM, 
     // vmcnt(KX) retires them
     if constexpr (PREF && P == 1)
       if ((it & (nch - 1)) == nch - 1) epi_prefetch(it);
-#ifndef EV_PIPE_LATE_ISSUE
     issue_weights(it1, lw0 + (1 - P) * WSLABP);
     if constexpr (WREG) issue_wreg(it1, std::integral_constant<int, WREG ? 1 - P : 0>());
     issue_halo(itp, std::integral_constant<int, SL_LD>());
-#endif
-    EV_TACC(tr_issue, tb0);
-    EV_T(tb1);
     float2 fs[4];
     stage_fs(std::integral_constant<int, SL_ST>(), fs);
     const char* lx = lx0 + P * xslab;
@@ -1139,13 +1071,6 @@ __global__ __launch_bounds__(NWV * 64, (MODE == ACT_FIRST || pipe_wreg(NWV, WM, 
       }
       bf16x8 (&a)[NPC][MF] = fa[fs_];
       bf16x8 (&b)[NPC][NF] = fb[fs_];
-#if defined(EV_PIPE_NOMFMA2)   // timing experiment only: no MFMA at all, the fragments kept live
-#pragma unroll
-      for (int mf = 0; mf < MF; ++mf)
-#pragma unroll
-        for (int nf = 0; nf < NF; ++nf)
-          acc[mf][nf][0] += (float)a[0][mf][0] * (float)b[0][nf][0] + (float)a[1][mf][1] * (float)b[1][nf][1];
-#elif !defined(EV_PIPE_NOMFMA)   // timing experiment only: one MFMA per fragment pair (wrong results)
 #pragma unroll
       for (int mf = 0; mf < MF; ++mf)
 #pragma unroll
@@ -1159,48 +1084,14 @@ __global__ __launch_bounds__(NWV * 64, (MODE == ACT_FIRST || pipe_wreg(NWV, WM, 
           acc[mf][nf] = mfma_piece<NP>(a[0][mf], b[1][nf], acc[mf][nf]);
           acc[mf][nf] = mfma_piece<NP>(a[0][mf], b[0][nf], acc[mf][nf]);
         }
-#else
-#pragma unroll
-      for (int mf = 0; mf < MF; ++mf)
-#pragma unroll
-        for (int nf = 0; nf < NF; ++nf) acc[mf][nf] = mfma_piece<NP>(a[0][mf] + a[1][mf], b[0][nf] + b[1][nf], acc[mf][nf]);
-#endif
-#ifdef EV_PIPE_LATE_ISSUE
-      if (s == 0) {   // behind the first k-step's MFMAs, so the matrix pipe covers the issue
-        issue_weights(it1, lw0 + (1 - P) * WSLABP);
-        issue_halo(itp, std::integral_constant<int, SL_LD>());
-      }
-#endif
       // staging of it+1, spread over the k-steps (PD = 1: its loads were issued this
-      // iteration, so stage after the last k-step's MFMAs are queued)
-#ifndef EV_PIPE_NOSTAGE   // timing experiment only: no staging VALU (wrong results)
-      // every item is staged (dead ones load nothing and write the dummy record), so the
-      // region has no branch
+      // iteration, so stage after the last k-step's MFMAs are queued); every item is staged
+      // (dead ones load nothing and write the dummy record), so the region has no branch
 #pragma unroll
       for (int k = 0; k < KX; ++k)
         if ((PD == 2 ? (k * 5) / KX : 4) == s)
           stage_item(std::integral_constant<int, SL_ST>(), k, fs, lxn);
-#endif
-#ifdef EV_PIPE_GROUPS   // experiment: measured slower for the input-gradient convs
-      // interleave: the next k-step's fragment reads, then each MFMA followed by its share of
-      // the staging VALU, so the vector work issues in the matrix pipe's shadow
-      {
-        constexpr int NMF = MF * NF * (NP == 3 ? 6 : 3);
-        constexpr int NIS = pipe_items_at(s, KX, PD);
-        constexpr int VPI = (NORM ? 12 : 0) + (POOL ? 12 : 0) + (GS ? 4 : 0) + (NPC == 2 ? 6 : 12);
-        constexpr int VPM = (NIS * VPI + NMF - 1) / NMF;
-        if constexpr (FPF && s + 1 < 5)
-          __builtin_amdgcn_sched_group_barrier(0x100, NPC * (MF + NF), 0);   // DS reads
-#pragma unroll
-        for (int i = 0; i < NMF; ++i) {
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                   // MFMA
-          if (VPM) __builtin_amdgcn_sched_group_barrier(0x002, VPM, 0);       // VALU
-        }
-      }
-#endif
-#ifndef EV_PIPE_NO_SCHED_FENCE
       __builtin_amdgcn_sched_barrier(0);   // one scheduling region per k-step (VGPR budget)
-#endif
     };
     kstep(std::integral_constant<int, 0>());
     kstep(std::integral_constant<int, 1>());
@@ -1214,13 +1105,7 @@ __global__ __launch_bounds__(NWV * 64, (MODE == ACT_FIRST || pipe_wreg(NWV, WM, 
         xt_pend = -1;
       }
     }
-    EV_TACC(tr_k, tb1);
-    EV_T(tb2);
-#ifdef EV_PIPE_NOBAR   // timing experiment only: no barrier (LDS races, wrong results)
-    if (false) {
-#else
     if (PD == 2) {
-#endif
       // the halo loads of it+2 (this wave's youngest vector-memory ops) stay in flight across
       // the barrier: everything older -- the weight DMA of it+1, epilogue traffic -- is retired
       // (resident weights: no DMA to wait for)
@@ -1229,18 +1114,10 @@ __global__ __launch_bounds__(NWV * 64, (MODE == ACT_FIRST || pipe_wreg(NWV, WM, 
       else
         pipe_barrier<(PD == 2 ? NLD : 0)>();
     } else {
-#ifndef EV_PIPE_NOBAR
       __syncthreads();
-#endif
     }
-    EV_TACC(tr_bar, tb2);
   };
 
-#ifdef EV_PIPE_PRIO
-  // the younger half of the workgroup loses VALU arbitration to the older half on every
-  // segment (MI355X_MICROARCH.md, two waves per SIMD): raise it once
-  if (wave_u >= NWV / 2) __builtin_amdgcn_s_setprio(1);   // scalar branch: this wave only
-#endif
   // the zero-padding columns of both halo buffers (never staged; every chunk and tile of the
   // block has them at the same records): 16-B granules of the NPC piece slots
   {
@@ -1300,10 +1177,8 @@ __global__ __launch_bounds__(NWV * 64, (MODE == ACT_FIRST || pipe_wreg(NWV, WM, 
       body(tl * nch + ch + 1, std::integral_constant<int, 1>());
     }
     // after the tile's last barrier: the stores drain under the next tile's MFMAs
-    EV_T(te0);
     epilogue(tl * nch, acc);
     zero_acc();
-    EV_TACC(tr_epi, te0);
   }
   // InstanceNorm finalize of the images this block owns (the host passes st_out / bst_out
   // only when every block's tile run covers whole images, pipe_owns_images): the forward
@@ -1329,14 +1204,6 @@ __global__ __launch_bounds__(NWV * 64, (MODE == ACT_FIRST || pipe_wreg(NWV, WM, 
                                 reinterpret_cast<double*>(xsm));
       }
   }
-#ifdef EV_PIPE_TRACE
-  if (lane == 0 && blockIdx.x < 4096) {
-    unsigned long long* o = ev_pipe_trace + ((size_t)blockIdx.x * 8 + (wave & 7)) * 6;
-    o[0] = __builtin_amdgcn_s_memtime() - tr_start;
-    o[1] = tr_issue; o[2] = tr_k; o[3] = tr_bar; o[4] = tr_epi;
-    o[5] = __builtin_amdgcn_s_memrealtime() - tr_rstart;   // 100 MHz
-  }
-#endif
 }
 
 // NP_F16 packs, step 1: partial maxima of |w| per layer, kF16MaxParts blocks per layer, into
@@ -1416,37 +1283,25 @@ __global__ void pack_split_kernel(const PackBatch pb, int np) {
 
 // EBSDVAE_CONV_PIPE=0 selects the non-persistent conv3x3_split_kernel (A/B timing)
 static bool use_pipe() {
-  static const int v = [] {
-    const char* e = getenv("EBSDVAE_CONV_PIPE");
-    return (e && e[0] == '0') ? 0 : 1;
-  }();
-  return v != 0;
+  static const bool v = evh::env_flag("EBSDVAE_CONV_PIPE", true);
+  return v;
 }
 
 // EBSDVAE_CONV_MULTI_IMAGE=0: 8x8 maps go to the fp32 small-map kernels (A/B timing)
 // EBSDVAE_CONV_SMALL1=0: the 8x8 split-fp16 convs keep two-image tiles (A/B)
 static bool use_small_one_image() {
-  static const bool v = [] {
-    const char* e = getenv("EBSDVAE_CONV_SMALL1");
-    return !(e && e[0] == '0');
-  }();
+  static const bool v = evh::env_flag("EBSDVAE_CONV_SMALL1", true);
   return v;
 }
 
 static bool use_multi_image() {
-  static const int v = [] {
-    const char* e = getenv("EBSDVAE_CONV_MULTI_IMAGE");
-    return (e && e[0] == '0') ? 0 : 1;
-  }();
-  return v != 0;
+  static const bool v = evh::env_flag("EBSDVAE_CONV_MULTI_IMAGE", true);
+  return v;
 }
 
 // EBSDVAE_WRES=0: Cin = 32 split-fp16 layers stream their weight slab per chunk (A/B timing)
 static bool use_wres() {
-  static const bool v = [] {
-    const char* e = getenv("EBSDVAE_WRES");
-    return !(e && e[0] == '0');
-  }();
+  static const bool v = evh::env_flag("EBSDVAE_WRES", true);
   return v;
 }
 
@@ -1543,10 +1398,7 @@ static bool plan_split(int H, int W, int cin, int cout, int np, X3Cfg* c) {
 // 4 rows per image, 8192 tiles over 256 CUs -> exactly one image per block.)
 // EBSDVAE_FUSE_FINALIZE=0 always takes the standalone finalize kernels (A/B, tests).
 static bool pipe_owns_images(const X3Cfg& c, int B, int H, hipStream_t s) {
-  static const bool on = [] {
-    const char* e = getenv("EBSDVAE_FUSE_FINALIZE");
-    return !(e && e[0] == '0');
-  }();
+  static const bool on = evh::env_flag("EBSDVAE_FUSE_FINALIZE", true);
   if (!on || !(c.NI > 1 || (use_pipe() && c.lds_pipe))) return false;
   const int tpi = c.NI > 1 ? 1 : H / c.TH;
   const int ntiles = ((B + c.NI - 1) / c.NI) * tpi;
@@ -1600,31 +1452,30 @@ template <int NP, int NWV, int WM, int MF, int NF, int KX, int NI = 1, int WR = 
 static void launch_x3(const X3Cfg& c, const float* src, const float* st, int mode, const void* wp,
                       const float* bias, float* y, float* part, float* aout, int B, int H, int W,
                       int cin, hipStream_t s, int pmode, const InBwdFuse& f) {
-  if (pmode >= 0) {
-    switch (pmode) {
-      case P_ID: launch_x3_1<NP, NWV, WM, MF, NF, KX, ACT_RAW, P_ID, NI, WR>(c, src, nullptr, wp, nullptr, y, nullptr, nullptr, B, H, W, cin, s, f); break;
-      case P_POOL: launch_x3_1<NP, NWV, WM, MF, NF, KX, ACT_RAW, P_POOL, NI, WR>(c, src, nullptr, wp, nullptr, y, nullptr, nullptr, B, H, W, cin, s, f); break;
-      case P_UPSUM:
-        if constexpr (NI == 1)
-          launch_x3_1<NP, NWV, WM, MF, NF, KX, ACT_RAW, FP_UPSUM, NI, WR>(c, src, nullptr, wp, nullptr, y, nullptr, nullptr, B, H, W, cin, s, f);
-        break;
-      default: launch_x3_1<NP, NWV, WM, MF, NF, KX, ACT_RAW, P_UP, NI, WR>(c, src, nullptr, wp, nullptr, y, nullptr, nullptr, B, H, W, cin, s, f); break;
-    }
+  // one geometry, every (source mode, fused epilogue): the pooled source never has resident weights
+  auto go = [&](auto mode_c, auto fp_c, const float* st_, const float* bias_, float* part_, float* aout_) {
+    constexpr int M = decltype(mode_c)::value, FP = decltype(fp_c)::value;
+    launch_x3_1<NP, NWV, WM, MF, NF, KX, M, FP, NI, M == ACT_NORM_POOL ? 0 : WR>(
+        c, src, st_, wp, bias_, y, part_, aout_, B, H, W, cin, s, f);
+  };
+  auto raw = std::integral_constant<int, ACT_RAW>();
+  if (pmode >= 0) {   // input gradient: raw source, no bias, statistics or activation output
+    evh::with_const<P_ID, P_POOL, P_UPSUM, P_UP>(pmode, [&](auto p_c) {
+      constexpr int P = decltype(p_c)::value, FP = P == P_UPSUM ? FP_UPSUM : P;
+      if constexpr (P != P_UPSUM || NI == 1)   // no summed upsample adjoint on two-image tiles
+        go(raw, std::integral_constant<int, FP>(), nullptr, nullptr, nullptr, nullptr);
+    });
     return;
   }
   if constexpr (NI == 1) {
     if (f.ypool) {   // producer of a max-pooled layer (ebsdvae_conv3x3_fwd_split_pooled)
-      launch_x3_1<NP, NWV, WM, MF, NF, KX, ACT_NORM, FP_POOLOUT, NI, WR>(c, src, st, wp, bias, y, part, aout, B, H, W, cin, s, f);
+      go(std::integral_constant<int, ACT_NORM>(), std::integral_constant<int, FP_POOLOUT>(), st, bias, part, aout);
       return;
     }
   }
-  switch (mode) {
-    case ACT_RAW: launch_x3_1<NP, NWV, WM, MF, NF, KX, ACT_RAW, FP_NONE, NI, WR>(c, src, st, wp, bias, y, part, aout, B, H, W, cin, s, f); break;
-    case ACT_NORM: launch_x3_1<NP, NWV, WM, MF, NF, KX, ACT_NORM, FP_NONE, NI, WR>(c, src, st, wp, bias, y, part, aout, B, H, W, cin, s, f); break;
-    case ACT_NORM_POOL: launch_x3_1<NP, NWV, WM, MF, NF, KX, ACT_NORM_POOL, FP_NONE, NI, 0>(c, src, st, wp, bias, y, part, aout, B, H, W, cin, s, f); break;
-    case ACT_UP: launch_x3_1<NP, NWV, WM, MF, NF, KX, ACT_UP, FP_NONE, NI, WR>(c, src, st, wp, bias, y, part, aout, B, H, W, cin, s, f); break;
-    default: launch_x3_1<NP, NWV, WM, MF, NF, KX, ACT_NORM_UP, FP_NONE, NI, WR>(c, src, st, wp, bias, y, part, aout, B, H, W, cin, s, f); break;
-  }
+  evh::with_const<ACT_RAW, ACT_NORM, ACT_NORM_POOL, ACT_UP, ACT_NORM_UP>(mode, [&](auto m_c) {
+    go(m_c, std::integral_constant<int, FP_NONE>(), st, bias, part, aout);
+  });
 }
 
 static void dispatch_split(const X3Cfg& c, int np, const float* src, const float* st, int mode,
@@ -1672,13 +1523,6 @@ static void dispatch_split(const X3Cfg& c, int np, const float* src, const float
 }  // namespace ev
 
 using namespace ev;
-
-#ifdef EV_PIPE_TRACE
-extern "C" int ebsdvae_debug_pipe_trace(void* host, size_t bytes) {
-  if (bytes > sizeof(ev_pipe_trace)) bytes = sizeof(ev_pipe_trace);
-  return hipMemcpyFromSymbol(host, HIP_SYMBOL(ev_pipe_trace), bytes, 0, hipMemcpyDeviceToHost) == hipSuccess ? 0 : 1;
-}
-#endif
 
 extern "C" int ebsdvae_conv3x3_split_supported(int H, int W, int cin, int cout, int pieces) {
   X3Cfg c;

@@ -35,12 +35,8 @@ struct WgGeom {
 // 64) stages 20 % fewer activation pixels than 2x32 (136) and measured 4-5 % faster on the
 // 128x128 layers (tools/conv_micro.py wgrad32, wgrad32u); EBSDVAE_WG_TW=32|8 for A/B timing
 static int wg_tw_pref() {
-  static const int v = [] {
-    const char* e = getenv("EBSDVAE_WG_TW");
-    const int t = e ? atoi(e) : 16;
-    return (t == 8 || t == 32) ? t : 16;
-  }();
-  return v;
+  static const int v = evh::env_int("EBSDVAE_WG_TW", 16, 8, 32);
+  return (v == 8 || v == 32) ? v : 16;
 }
 
 // target block count of a weight-gradient launch (slices x co tiles x ci tiles).  Every
@@ -48,11 +44,8 @@ static int wg_tw_pref() {
 // cut that traffic (512 measured 0.2 ms/step faster than 1024; 256 leaves half the CUs'
 // block slots empty); EBSDVAE_WG_BLOCKS overrides the split kernels' target (A/B timing)
 static int wg_block_target(int pt) {
-  static const int v = [] {
-    const char* e = getenv("EBSDVAE_WG_BLOCKS");
-    const int t = e ? atoi(e) : 512;   // 2 blocks per CU x 256 CUs: one wave of blocks
-    return (t >= 64 && t <= 8192) ? t : 512;
-  }();
+  // 512 = 2 blocks per CU x 256 CUs: one wave of blocks
+  static const int v = evh::env_int("EBSDVAE_WG_BLOCKS", 512, 64, 8192);
   return pt == 64 ? v : 1024;
 }
 
@@ -94,10 +87,7 @@ static bool wg_geom(int B, int H, int W, int cin, int cout, WgGeom* g, int pt = 
 // the pipelined two-piece kernel (wgrad_pipe_kernel) on 8x8 tiles; EBSDVAE_WG_PIPE=0 selects
 // wgrad_split_kernel instead (A/B timing)
 static bool wg_pipe() {
-  static const bool v = [] {
-    const char* e = getenv("EBSDVAE_WG_PIPE");
-    return !(e && e[0] == '0');
-  }();
+  static const bool v = evh::env_flag("EBSDVAE_WG_PIPE", true);
   return v;
 }
 // output channels per block of the pipelined kernel: 32 (cout 32), 128 (8-wave blocks, one per
@@ -108,28 +98,20 @@ static bool wg_pipe() {
 // schedule (kernel-attached forks, fused network end) the step is 0.07 ms faster with them
 // (two pairs, same box), so they are the default.
 static int wg_pipe_cot(int cout) {
-  static const bool wide = [] {
-    const char* e = getenv("EBSDVAE_WG_CO128");
-    return !(e && e[0] == '0');
-  }();
+  static const bool wide = evh::env_flag("EBSDVAE_WG_CO128", true);
   return cout == 32 ? 32 : ((wide && cout % 128 == 0) ? 128 : 64);
 }
 // input channels per block of the pipelined kernel: 64 for co 64 blocks where cin % 64 == 0
 // (co 64 x ci 64, 8 waves: gy is read once per layer instead of twice; 64->64 @64 236 -> 221 us,
-// round 5), else 32.  A co 128 x ci 64 block (waves of co 64 x ci 16) needs 144 accumulator
-// VGPRs and spilled 132-208 B per lane: 2x slower (wgrad128 195 -> 400 us), not used.
-// EBSDVAE_WG_CI64=0: always 32 (A/B); =2 also the co 128 x ci 64 blocks (experiment)
+// round 5), else 32.  co 128 x ci 64 blocks spilled and ran 2x slower (wgrad128 195 -> 400 us).
+// EBSDVAE_WG_CI64=0: always 32 (A/B); any other value is the default
 static int wg_pipe_ci64_mode() {
-  static const int v = [] {
-    const char* e = getenv("EBSDVAE_WG_CI64");
-    return e ? atoi(e) : 1;
-  }();
+  static const int v = evh::env_int("EBSDVAE_WG_CI64", 1, 0, 1);
   return v;
 }
 static int wg_pipe_cit(int cin, int cout) {
-  const int m = wg_pipe_ci64_mode();
-  if (m <= 0 || cout == 32 || cin % 64) return 32;
-  return (m >= 2 || wg_pipe_cot(cout) == 64) ? 64 : 32;
+  if (wg_pipe_ci64_mode() == 0 || cout == 32 || cin % 64) return 32;
+  return wg_pipe_cot(cout) == 64 ? 64 : 32;
 }
 static bool wg_pipe_geom(int B, int H, int W, int cin, int cout, WgGeom* g) {
   if (B <= 0 || H <= 0 || W <= 0 || cin <= 0 || cout <= 0) return false;
@@ -249,12 +231,8 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(
       const int img = px / T::IPX, rem = px % T::IPX;
       const int r = rem / TW, c = rem % TW;
       const int gb = b0 + img;
-#ifdef EV_WG_NOLOAD   // timing experiment only (wrong results)
-      rg[k] = make_float4((float)r, (float)c, 1.f, 0.f);
-#else
       if (T::NI == 1 || gb < B)
         rg[k] = ld4(gy + (((size_t)gb * H + y0 + r) * W + x0 + c) * Cout + co0 + qg * 4);
-#endif
     }
 #pragma unroll
     for (int k = 0; k < KH; ++k) {
@@ -264,11 +242,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(
       const int gh = y0 + hh - 1, gw = x0 + ww - 1, gb = b0 + img;
       if (pix < T::HALO && gb < B && gh >= 0 && gh < H && gw >= 0 && gw < W) {
         const int sh = UPS ? (gh >> 1) : gh, sw = UPS ? (gw >> 1) : gw;
-#ifdef EV_WG_NOLOAD
-        rh[k] = make_float4((float)sh, (float)sw, 1.f, 0.f);
-#else
         rh[k] = ld4(src + (((size_t)gb * Hs + sh) * Ws + sw) * Cin + ci0 + qh * 4);
-#endif
       }
     }
     if (NORM && T::NI == 1) load_stats(b0);
@@ -607,12 +581,8 @@ __global__ __launch_bounds__(256, 2) void wgrad_split_kernel(
       const int img = px / T::IPX, rem = px % T::IPX;
       const int r = rem / TW, c = rem % TW;
       const int gb = b0 + img;
-#ifdef EV_WG_NOLOAD   // timing experiment only (wrong results)
-      rg[k] = make_float4((float)r, (float)c, 1.f, 0.f);
-#else
       if (T::NI == 1 || gb < B)
         rg[k] = ld4(gy + (((size_t)gb * H + y0 + r) * W + x0 + c) * Cout + co0 + qg * 4);
-#endif
     }
 #pragma unroll
     for (int k = 0; k < KH; ++k) {
@@ -622,11 +592,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_split_kernel(
       const int gh = y0 + hh - 1, gw = x0 + ww - 1, gb = b0 + img;
       if (pix < T::HALO && gb < B && gh >= 0 && gh < H && gw >= 0 && gw < W) {
         const int sh = UPS ? (gh >> 1) : gh, sw = UPS ? (gw >> 1) : gw;
-#ifdef EV_WG_NOLOAD
-        rh[k] = make_float4((float)sh, (float)sw, 1.f, 0.f);
-#else
         rh[k] = ld4(src + (((size_t)gb * Hs + sh) * Ws + sw) * Cin + ci0 + qh * 4);
-#endif
       }
     }
     if (NORM && T::NI == 1) load_stats(b0);
@@ -675,9 +641,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_split_kernel(
   if (t_beg < t_end) issue(t_beg);
   for (int t = t_beg; t < t_end; ++t) {
     __syncthreads();
-#ifndef EV_WG_NOSTORE   // timing experiment only: no staging (and so no loads; wrong results)
     store();
-#endif
     __syncthreads();
     if (t + 1 < t_end) issue(t + 1);
 #pragma unroll
@@ -701,20 +665,10 @@ __global__ __launch_bounds__(256, 2) void wgrad_split_kernel(
 #pragma unroll
       for (int tap = 0; tap < 9; ++tap) {
         const int toff = (tap / 3) * T::WP + tap % 3;
-#ifdef EV_WG_ONEB   // timing experiment only: one activation fragment per k-step (wrong results)
-        if (tap == 0)
-#endif
 #pragma unroll
         for (int i = 0; i < NPC; ++i)
           b[i] = tr_frag(aimg + i * ACT_PIECE + (hp0 + toff) * WGS_ASB + bcol,
                          aimg + i * ACT_PIECE + (hp1 + toff) * WGS_ASB + bcol);
-#ifdef EV_WG_NOMFMA   // timing experiment only (wrong results)
-#pragma unroll
-        for (int f = 0; f < 2; ++f)
-#pragma unroll
-          for (int i = 0; i < NPC; ++i) acc[f][tap][i & 3] += (float)a[i][f][0] * (float)b[i][1];
-        if (false)
-#endif
 #pragma unroll
         for (int f = 0; f < 2; ++f) {
           f32x4 c = acc[f][tap];
@@ -755,13 +709,11 @@ EV_DEVINL void static_for(F&& f) {
 // and each item's register is refilled with tile t+2's load as soon as it has been staged
 // (a whole tile of MFMA work covers every load).  One barrier per tile.  The serial kernel
 // spends most of its time there: without its staging it runs 2.3-2.7x faster, without its
-// loads 1.3x (tools/micro_variants.sh, EV_WG_NOSTORE / EV_WG_NOLOAD).
+// loads 1.3x (timing builds).
 // NWCO = 4 (co 128 x ci 32, 8 waves, one block per CU by LDS): the activation halo of a tile
 // is staged once per 128 output channels instead of once per 64 (EBSDVAE_WG_CO128).
-// NWCI = 4 (ci tile 64; round 5): with FCO = 4 (waves of co 64 x ci 16, 144 accumulator
-// registers) a co 128 x ci 64 block stages 0.64x the values per MAC of co 128 x ci 32 and reads
-// each B fragment for twice the MFMAs; with FCO = 2 a co 64 x ci 64 block reads gy once per
-// layer instead of twice (EBSDVAE_WG_CI64=0: the ci 32 blocks, A/B)
+// NWCI = 4 (ci tile 64; round 5), FCO = 2: a co 64 x ci 64 block reads gy once per layer instead
+// of twice (EBSDVAE_WG_CI64=0: the ci 32 blocks, A/B)
 // Staging-store order of the 8-B piece stores (ds_write_b64: 4 groups of 16 contiguous lanes,
 // banks (a/4) mod 32).  With 8 float4 items per pixel (32-channel images, 96-B rows) a group
 // stores two pixels, and consecutive pixels (rows 24 dwords apart) overlap in 8 banks: 2-way on
@@ -993,24 +945,18 @@ __global__ __launch_bounds__(NWCO * NWCI * KSPLIT * 64, NWCO * NWCI * KSPLIT >= 
 #pragma unroll
         for (int f = 0; f < FCO; ++f) {
           f32x4 c = acc[f][tap];
-#ifdef EV_WGP_NOMFMA   // timing experiment only (wrong results)
-          c[0] += (float)a[0][f][0] * (float)b[0][0] + (float)a[1][f][1] * (float)b[1][1];
-#else
           c = mfma16_piece<NP>(a[1][f], b[0], c);
           c = mfma16_piece<NP>(a[0][f], b[1], c);
           c = mfma16_piece<NP>(a[0][f], b[0], c);
-#endif
           acc[f][tap] = c;
         }
         // this slot's share of the staging: item j at slot j * NSLOT / NIT
         all_items([&](auto j_c) EV_LAMBDA_INLINE {
           constexpr int j = decltype(j_c)::value;
-#ifndef EV_WGP_NOSTAGE   // timing experiment only (wrong results)
           if constexpr (si * 9 + tap == (j * NSLOT) / NIT) {
             store_item(j_c, nbuf);
             issue_item(j_c);
           }
-#endif
         });
       });
     });
@@ -1373,67 +1319,39 @@ static void launch_wgp(dim3 grid, hipStream_t s, const float* src, const float* 
                      cin, cout, g, gmax, gmT);
 }
 
+// the source mode of a weight-gradient launch as a compile-time constant (the entry points refuse
+// ACT_NORM_POOL): f(std::integral_constant<int, MODE>)
+template <class F>
+static void with_src_mode(int mode, F&& f) {
+  evh::with_const<ACT_RAW, ACT_NORM, ACT_UP, ACT_NORM_UP>(mode, f);
+}
+template <int N> using Int = std::integral_constant<int, N>;
+
 template <int NP>
 static void dispatch_wgp(int mode, bool narrow, dim3 grid, hipStream_t s, const float* src,
                          const float* st, const float* gy, float* wpart, float* bpart, int B, int H,
                          int W, int cin, int cout, const WgGeom& g, const float* gmax, int gmT) {
-  if (narrow) {
-    switch (mode) {
-      case ACT_RAW: launch_wgp<NP, 1, 2, ACT_RAW>(grid, s, src, st, gy, wpart, bpart, B, H, W, cin, cout, g, gmax, gmT); break;
-      case ACT_NORM: launch_wgp<NP, 1, 2, ACT_NORM>(grid, s, src, st, gy, wpart, bpart, B, H, W, cin, cout, g, gmax, gmT); break;
-      case ACT_UP: launch_wgp<NP, 1, 2, ACT_UP>(grid, s, src, st, gy, wpart, bpart, B, H, W, cin, cout, g, gmax, gmT); break;
-      default: launch_wgp<NP, 1, 2, ACT_NORM_UP>(grid, s, src, st, gy, wpart, bpart, B, H, W, cin, cout, g, gmax, gmT); break;
-    }
-  } else if (wg_pipe_cit(cin, cout) == 64 && wg_pipe_cot(cout) == 128) {   // co 128 x ci 64
-    switch (mode) {
-      case ACT_RAW: launch_wgp<NP, 2, 1, ACT_RAW, 4, 4>(grid, s, src, st, gy, wpart, bpart, B, H, W, cin, cout, g, gmax, gmT); break;
-      case ACT_NORM: launch_wgp<NP, 2, 1, ACT_NORM, 4, 4>(grid, s, src, st, gy, wpart, bpart, B, H, W, cin, cout, g, gmax, gmT); break;
-      case ACT_UP: launch_wgp<NP, 2, 1, ACT_UP, 4, 4>(grid, s, src, st, gy, wpart, bpart, B, H, W, cin, cout, g, gmax, gmT); break;
-      default: launch_wgp<NP, 2, 1, ACT_NORM_UP, 4, 4>(grid, s, src, st, gy, wpart, bpart, B, H, W, cin, cout, g, gmax, gmT); break;
-    }
-  } else if (wg_pipe_cit(cin, cout) == 64) {   // co 64 x ci 64
-    switch (mode) {
-      case ACT_RAW: launch_wgp<NP, 2, 1, ACT_RAW, 4, 2>(grid, s, src, st, gy, wpart, bpart, B, H, W, cin, cout, g, gmax, gmT); break;
-      case ACT_NORM: launch_wgp<NP, 2, 1, ACT_NORM, 4, 2>(grid, s, src, st, gy, wpart, bpart, B, H, W, cin, cout, g, gmax, gmT); break;
-      case ACT_UP: launch_wgp<NP, 2, 1, ACT_UP, 4, 2>(grid, s, src, st, gy, wpart, bpart, B, H, W, cin, cout, g, gmax, gmT); break;
-      default: launch_wgp<NP, 2, 1, ACT_NORM_UP, 4, 2>(grid, s, src, st, gy, wpart, bpart, B, H, W, cin, cout, g, gmax, gmT); break;
-    }
-  } else if (wg_pipe_cot(cout) == 128) {
-    switch (mode) {
-      case ACT_RAW: launch_wgp<NP, 4, 1, ACT_RAW>(grid, s, src, st, gy, wpart, bpart, B, H, W, cin, cout, g, gmax, gmT); break;
-      case ACT_NORM: launch_wgp<NP, 4, 1, ACT_NORM>(grid, s, src, st, gy, wpart, bpart, B, H, W, cin, cout, g, gmax, gmT); break;
-      case ACT_UP: launch_wgp<NP, 4, 1, ACT_UP>(grid, s, src, st, gy, wpart, bpart, B, H, W, cin, cout, g, gmax, gmT); break;
-      default: launch_wgp<NP, 4, 1, ACT_NORM_UP>(grid, s, src, st, gy, wpart, bpart, B, H, W, cin, cout, g, gmax, gmT); break;
-    }
-  } else {
-    switch (mode) {
-      case ACT_RAW: launch_wgp<NP, 2, 1, ACT_RAW>(grid, s, src, st, gy, wpart, bpart, B, H, W, cin, cout, g, gmax, gmT); break;
-      case ACT_NORM: launch_wgp<NP, 2, 1, ACT_NORM>(grid, s, src, st, gy, wpart, bpart, B, H, W, cin, cout, g, gmax, gmT); break;
-      case ACT_UP: launch_wgp<NP, 2, 1, ACT_UP>(grid, s, src, st, gy, wpart, bpart, B, H, W, cin, cout, g, gmax, gmT); break;
-      default: launch_wgp<NP, 2, 1, ACT_NORM_UP>(grid, s, src, st, gy, wpart, bpart, B, H, W, cin, cout, g, gmax, gmT); break;
-    }
-  }
+  with_src_mode(mode, [&](auto m) {
+    auto go = [&](auto nwco, auto ksplit, auto nwci) {
+      launch_wgp<NP, decltype(nwco)::value, decltype(ksplit)::value, decltype(m)::value,
+                 decltype(nwci)::value>(grid, s, src, st, gy, wpart, bpart, B, H, W, cin, cout, g, gmax, gmT);
+    };
+    if (narrow) go(Int<1>(), Int<2>(), Int<2>());
+    else if (wg_pipe_cit(cin, cout) == 64) go(Int<2>(), Int<1>(), Int<4>());   // co 64 x ci 64
+    else if (wg_pipe_cot(cout) == 128) go(Int<4>(), Int<1>(), Int<2>());
+    else go(Int<2>(), Int<1>(), Int<2>());
+  });
 }
 
 template <int NP>
 static void dispatch_wgs(int mode, bool narrow, dim3 grid, hipStream_t s, const float* src,
                          const float* st, const float* gy, float* wpart, float* bpart, int B, int H,
                          int W, int cin, int cout, const WgGeom& g, const float* gmax, int gmT) {
-  if (narrow) {
-    switch (mode) {
-      case ACT_RAW: launch_wgs<NP, 1, 2, ACT_RAW>(grid, s, src, st, gy, wpart, bpart, B, H, W, cin, cout, g, gmax, gmT); break;
-      case ACT_NORM: launch_wgs<NP, 1, 2, ACT_NORM>(grid, s, src, st, gy, wpart, bpart, B, H, W, cin, cout, g, gmax, gmT); break;
-      case ACT_UP: launch_wgs<NP, 1, 2, ACT_UP>(grid, s, src, st, gy, wpart, bpart, B, H, W, cin, cout, g, gmax, gmT); break;
-      default: launch_wgs<NP, 1, 2, ACT_NORM_UP>(grid, s, src, st, gy, wpart, bpart, B, H, W, cin, cout, g, gmax, gmT); break;
-    }
-  } else {
-    switch (mode) {
-      case ACT_RAW: launch_wgs<NP, 2, 1, ACT_RAW>(grid, s, src, st, gy, wpart, bpart, B, H, W, cin, cout, g, gmax, gmT); break;
-      case ACT_NORM: launch_wgs<NP, 2, 1, ACT_NORM>(grid, s, src, st, gy, wpart, bpart, B, H, W, cin, cout, g, gmax, gmT); break;
-      case ACT_UP: launch_wgs<NP, 2, 1, ACT_UP>(grid, s, src, st, gy, wpart, bpart, B, H, W, cin, cout, g, gmax, gmT); break;
-      default: launch_wgs<NP, 2, 1, ACT_NORM_UP>(grid, s, src, st, gy, wpart, bpart, B, H, W, cin, cout, g, gmax, gmT); break;
-    }
-  }
+  with_src_mode(mode, [&](auto m) {
+    constexpr int M = decltype(m)::value;
+    if (narrow) launch_wgs<NP, 1, 2, M>(grid, s, src, st, gy, wpart, bpart, B, H, W, cin, cout, g, gmax, gmT);
+    else launch_wgs<NP, 2, 1, M>(grid, s, src, st, gy, wpart, bpart, B, H, W, cin, cout, g, gmax, gmT);
+  });
 }
 
 static bool wgs_geom_ok(const WgGeom& g, int pt) {
@@ -1559,25 +1477,14 @@ extern "C" int ebsdvae_conv3x3_wgrad(const float* src, const float* src_stats, i
              "conv3x3_wgrad: unsupported tile geometry H=%d W=%d", H, W);
   EV_REQUIRE(src_mode != ACT_NORM_POOL,
              "conv3x3_wgrad: pass the pooled activation materialised by the forward (RAW)");
-  if (cout == 32 || g.TW == 8) {
-    const size_t lds = wg_lds(0, g, 32);
-    const dim3 grid(g.slices, cout / 32, cin / 32);
-    switch (src_mode) {
-      case ACT_RAW: launch_wg<1, 2, ACT_RAW>(grid, lds, s, src, src_stats, gy, wpart, bpart, B, H, W, cin, cout, g); break;
-      case ACT_NORM: launch_wg<1, 2, ACT_NORM>(grid, lds, s, src, src_stats, gy, wpart, bpart, B, H, W, cin, cout, g); break;
-      case ACT_UP: launch_wg<1, 2, ACT_UP>(grid, lds, s, src, src_stats, gy, wpart, bpart, B, H, W, cin, cout, g); break;
-      default: launch_wg<1, 2, ACT_NORM_UP>(grid, lds, s, src, src_stats, gy, wpart, bpart, B, H, W, cin, cout, g); break;
-    }
-  } else {
-    const size_t lds = wg_lds(0, g, 64);
-    const dim3 grid(g.slices, cout / 64, cin / 32);
-    switch (src_mode) {
-      case ACT_RAW: launch_wg<2, 1, ACT_RAW>(grid, lds, s, src, src_stats, gy, wpart, bpart, B, H, W, cin, cout, g); break;
-      case ACT_NORM: launch_wg<2, 1, ACT_NORM>(grid, lds, s, src, src_stats, gy, wpart, bpart, B, H, W, cin, cout, g); break;
-      case ACT_UP: launch_wg<2, 1, ACT_UP>(grid, lds, s, src, src_stats, gy, wpart, bpart, B, H, W, cin, cout, g); break;
-      default: launch_wg<2, 1, ACT_NORM_UP>(grid, lds, s, src, src_stats, gy, wpart, bpart, B, H, W, cin, cout, g); break;
-    }
-  }
+  const bool narrow = cout == 32 || g.TW == 8;
+  const size_t lds = wg_lds(0, g, narrow ? 32 : 64);
+  const dim3 grid(g.slices, cout / (narrow ? 32 : 64), cin / 32);
+  with_src_mode(src_mode, [&](auto m) {
+    constexpr int M = decltype(m)::value;
+    if (narrow) launch_wg<1, 2, M>(grid, lds, s, src, src_stats, gy, wpart, bpart, B, H, W, cin, cout, g);
+    else launch_wg<2, 1, M>(grid, lds, s, src, src_stats, gy, wpart, bpart, B, H, W, cin, cout, g);
+  });
   return evh::check_launch("wgrad");
 }
 

@@ -37,13 +37,7 @@ constexpr int NE_C = 32, NE_TH = EV_NE_TH, NE_TH_MIN = 32;
 #endif
 constexpr int NE_FOLD = EV_NE_FOLD;   // rows per running sum of net_end_mfma_kernel (power of two)
 constexpr int ne_th(int H) { return H % NE_TH == 0 ? NE_TH : NE_TH_MIN; }
-constexpr int NE_RING = 4;
-#ifndef EV_NE_UNROLL6
-#define EV_NE_UNROLL6 1
-#endif
-#ifndef EV_NE_BRFREE
-#define EV_NE_BRFREE 1
-#endif                 // ring slots (a and g1): slot(row) = (row - r0 + k) & 3
+constexpr int NE_RING = 4;   // ring slots (a and g1): slot(row) = (row - r0 + k) & 3
 // per width: threads, ring row (zero column, W pixels, zero column)
 template <int W> constexpr int ne_nth() { return 2 * W; }
 template <int W> constexpr int ne_wp() { return W + 2; }
@@ -637,7 +631,6 @@ __global__ __launch_bounds__(2 * W, W == 128 ? 2 : 1) void net_end_mfma_kernel(
         // S[t] = sum over own rows c of g1[c - d_t]: row r feeds tap row kh when
         // r in [r0 + 1 - kh, r0 + TH + 1 - kh), column w feeds kw unless the shifted
         // column falls outside the image (w = 0 for kw = 0, w = W - 1 for kw = 2)
-#if EV_NE_BRFREE
         const float gl = g * ml, gr_ = g * mr;
 #pragma unroll
         for (int kh = 0; kh < 3; ++kh)
@@ -646,15 +639,6 @@ __global__ __launch_bounds__(2 * W, W == 128 ? 2 : 1) void net_end_mfma_kernel(
             S[3 * kh] += gl;
             S[3 * kh + 2] += gr_;
           }
-#else
-#pragma unroll
-        for (int kh = 0; kh < 3; ++kh)
-          if (r >= r0 + 1 - kh && r < r0 + TH + 1 - kh) {
-            S[3 * kh + 1] += g;
-            if (w != 0) S[3 * kh] += g;
-            if (w != W - 1) S[3 * kh + 2] += g;
-          }
-#endif
         // g1 * 2^kg as two fp16 pieces into the three column-shifted copies of slot r & 3:
         // copy kw holds g1[x + 1 - kw] at x, stored at x + 4 (8-byte aligned fragment reads): the
         // writes to x = -1 and x = W land in pad entries no fragment reads, so they need no test
@@ -664,14 +648,8 @@ __global__ __launch_bounds__(2 * W, W == 128 ? 2 : 1) void net_end_mfma_kernel(
         _Float16* gr = gring + (size_t)(r & 3) * 6 * GRS + w + 3;
 #pragma unroll
         for (int kw = 0; kw < 3; ++kw) {
-#if !EV_NE_BRFREE
-          const int x = w - 1 + kw;
-          if (x >= 0 && x < W)
-#endif
-          {
-            gr[(kw * 2 + 0) * GRS + kw] = q0;
-            gr[(kw * 2 + 1) * GRS + kw] = q1;
-          }
+          gr[(kw * 2 + 0) * GRS + kw] = q0;
+          gr[(kw * 2 + 1) * GRS + kw] = q1;
         }
       }
     }
@@ -723,23 +701,6 @@ __global__ __launch_bounds__(2 * W, W == 128 ? 2 : 1) void net_end_mfma_kernel(
     put_image(pb);
   };
   constexpr int NS = TH + 6, NM = NS - NS % 6;   // steps; those of the six-step loop
-#if !EV_NE_UNROLL6
-  auto rot = [&]() EV_LAMBDA_INLINE {
-#pragma unroll
-    for (int t3 = 0; t3 < 3; ++t3)
-#pragma unroll
-      for (int g = 0; g < 2; ++g) { R2[t3][g] = R1[t3][g]; R1[t3][g] = R0[t3][g]; }
-  };
-  (void)R2;
-  static_assert(NS % 2 == 0, "two-step loop");
-#pragma unroll 1
-  for (int i = 0; i < NS; i += 2) {
-    step(i, ybuf[0], tbuf[0], R0, R2);
-    rot();
-    step(i + 1, ybuf[1], tbuf[1], R0, R2);
-    rot();
-  }
-#else
 #pragma unroll 1
   for (int i = 0; i < NM; i += 6) {
     step(i, ybuf[0], tbuf[0], R0, R1);
@@ -754,7 +715,6 @@ __global__ __launch_bounds__(2 * W, W == 128 ? 2 : 1) void net_end_mfma_kernel(
   if constexpr (NS % 6 > 2) step(NM + 2, ybuf[0], tbuf[0], R2, R0);
   if constexpr (NS % 6 > 3) step(NM + 3, ybuf[1], tbuf[1], R0, R1);
   if constexpr (NS % 6 > 4) step(NM + 4, ybuf[0], tbuf[0], R1, R2);
-#endif
   __syncthreads();
   // ---- band partials, fixed order
   // G / P: C/D of wave w, M block mb: channel 16 mb + 4 gq + k (k = 0..3), tap l16

@@ -3,9 +3,16 @@
 // launch).  Linked with the library objects built with -Xarch_host -fsanitize=address
 // (ebsd-vae_amd/build.py --asan); needs no GPU: every call below is a shape / size query or is
 // rejected by validation.  Exit 0 = all expectations held (ASan aborts on any memory error).
+//
+// With an argument, one run-time switch case instead: the library reads each EBSDVAE_* switch
+// once per process, so every case is a process of its own.  It sets the variable before the
+// first planner call and prints the planners' answers; tests/test_abi.py holds the expected
+// lines.
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 
+#include <string>
 #include <vector>
 
 #include "../../include/ebsdvae.h"
@@ -20,7 +27,32 @@ static void expect_err(int rc, const char* what) {
   }
 }
 
-int main() {
+// "<var>=<value>" (or "default"), then the weight-gradient slice counts and the split-conv
+// support answers of a fixed list of shapes
+static int switch_case(const char* kv) {
+  if (strcmp(kv, "default") != 0) {
+    const char* eq = strchr(kv, '=');
+    if (!eq) { printf("FAIL case '%s'\n", kv); return 1; }
+    const std::string var(kv, eq - kv);
+    setenv(var.c_str(), eq + 1, 1);
+  }
+  printf("slices");
+  const int hw[][2] = {{128, 128}, {2, 32}, {8, 8}};
+  const int cc[][2] = {{32, 32}, {64, 64}};
+  for (int B : {4, 256})
+    for (auto& s : hw)
+      for (auto& c : cc)
+        for (int p : {2, 3, EBSDVAE_PIECES_F16})
+          printf(" %d", ebsdvae_conv3x3_wgrad_split_slices(B, s[0], s[1], c[0], c[1], p));
+  printf("\nsupported");
+  for (int p : {2, 3, EBSDVAE_PIECES_F16})
+    printf(" %d", ebsdvae_conv3x3_split_supported(8, 8, 128, 128, p));
+  printf("\n");
+  return 0;
+}
+
+int main(int argc, char** argv) {
+  if (argc > 1) return switch_case(argv[1]);
   if (ebsdvae_version() != EBSDVAE_ABI_VERSION) { printf("FAIL version\n"); return 1; }
   const int sizes[] = {-8, 0, 1, 4, 7, 8, 16, 32, 64, 100, 128, 256, 512, 4096, 1 << 20};
   const int chans[] = {-1, 0, 1, 3, 8, 16, 32, 64, 96, 128, 256};

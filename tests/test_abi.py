@@ -103,6 +103,42 @@ def test_host_asan_driver():
     assert "abi_asan: ok" in r.stdout
 
 
+# The planners' answers under one run-time switch each (tests/asan/abi_asan.cpp <var>=<value>:
+# wgrad_split_slices of B 4 / 256 x (128x128, 2x32, 8x8) x (32->32, 64->64) x pieces (2, 3, f16),
+# then split_supported(8, 8, 128, 128, pieces)).  The expected lines are the answers of the
+# library as it stood before the switches went through evh::env_flag / env_int (commit 7608517),
+# recorded once; the out-of-range block target must give the default's.
+_DEFAULT_SLICES = ("slices 256 256 256 256 256 256 -1 -1 -1 -1 1 -1 1 1 1 1 1 1 "
+                   "512 512 512 256 256 256 -1 -1 -1 -1 64 -1 64 64 64 64 64 64")
+SWITCH_CASES = {
+    "default": (_DEFAULT_SLICES, "supported 0 1 1"),
+    "EBSDVAE_WG_TW=32": ("slices 256 256 256 256 256 256 -1 1 -1 -1 1 -1 1 1 1 1 1 1 "
+                         "512 512 512 256 256 256 -1 64 -1 -1 64 -1 64 64 64 64 64 64", "supported 0 1 1"),
+    "EBSDVAE_WG_BLOCKS=1024": ("slices 256 256 256 256 256 256 -1 -1 -1 -1 1 -1 1 1 1 1 1 1 "
+                               "1024 1024 1024 512 512 512 -1 -1 -1 -1 64 -1 64 64 64 64 64 64",
+                               "supported 0 1 1"),
+    "EBSDVAE_WG_BLOCKS=100000": (_DEFAULT_SLICES, "supported 0 1 1"),
+    "EBSDVAE_CONV_MULTI_IMAGE=0": (_DEFAULT_SLICES, "supported 0 0 0"),
+}
+
+
+@pytest.mark.parametrize("case", list(SWITCH_CASES))
+def test_host_asan_driver_switch_cases(case):
+    """The switch readers under host ASan, one process per case (each switch is read once)."""
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "ebsd-vae_amd"))
+    import build
+    try:
+        exe = build.build_asan(verbose=False)
+    except RuntimeError as e:      # pragma: no cover - toolchain missing
+        pytest.skip(f"hipcc unavailable: {e}")
+    env = {k: v for k, v in os.environ.items() if not k.startswith("EBSDVAE_")}
+    env["ASAN_OPTIONS"] = "detect_leaks=0:abort_on_error=0"
+    r = subprocess.run([exe, case], capture_output=True, text=True, timeout=300, env=env)
+    assert r.returncode == 0 and "AddressSanitizer" not in r.stderr, (r.stdout + r.stderr)[-4000:]
+    assert tuple(r.stdout.strip().split("\n")) == SWITCH_CASES[case]
+
+
 def test_query_entry_points_are_registered_as_queries():
     """Size / support queries return their value instead of a status: every one the signature
     table lists must be in _native.QUERIES, or N.call would raise on its (nonzero) answer."""

@@ -178,19 +178,6 @@ def run(name, reps, pieces, B, warm=1.0):
     e1.record()
     torch.cuda.synchronize()
     us = e0.elapsed_time(e1) * 1e3 / reps
-    lib = N.load()
-    if hasattr(lib, "ebsdvae_debug_pipe_trace"):   # EV_PIPE_TRACE build: per-wave cycle split
-        import numpy as np
-        buf = np.zeros(4096 * 8 * 6, dtype=np.uint64)
-        lib.ebsdvae_debug_pipe_trace(ctypes.c_void_p(buf.ctypes.data), ctypes.c_size_t(buf.nbytes))
-        t = buf.reshape(4096, 8, 6).astype(np.float64)
-        t = t[t[:, 0, 0] > 0]
-        tot = t[:, :, 0].mean()
-        clk = (t[:, :, 0] / (t[:, :, 5] / 100.0)).mean() / 1e3
-        print(f"   trace ({len(t)} blocks, clock {clk:.2f} GHz): total {tot:.0f} cyc; issue "
-              f"{t[:, :, 1].mean() / tot:.3f} kloop {t[:, :, 2].mean() / tot:.3f} barrier "
-              f"{t[:, :, 3].mean() / tot:.3f} epilogue {t[:, :, 4].mean() / tot:.3f}; per-wave barrier "
-              + " ".join(f"{v:.2f}" for v in (t[:, :, 3].mean(0) / tot)))
     peak = 2516.6 / {2: 3, 3: 6, 16: 3}[pieces]
     tf = flops / us / 1e6
     print(f"{name:12s} {kind:5s} {cin:3d}->{cout:3d} @{H:3d}  {us:8.1f} us  {tf:6.1f} TF/s  "
