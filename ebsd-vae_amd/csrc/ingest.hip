@@ -19,18 +19,10 @@
 // geometry and ToTensor's float32(v) / 255 alone (a true division), which is what the float
 // entry point gives for v / 255.0 -- (v / 255.0) * 255.0 truncates back to v for all 256 values.
 #include "common.h"
+#include "crop.h"
 #include "../../include/ebsdvae.h"
 
 namespace ev {
-
-// torchvision center_crop source offset along one axis (negative = leading zero padding)
-static int crop_offset(int size, int crop) {
-  if (crop > size) return -((crop - size) / 2);
-  const int d = size - crop;             // round(d / 2.0), ties to even
-  const int h = d / 2;
-  if ((d & 1) == 0) return h;
-  return (h & 1) == 0 ? h : h + 1;
-}
 
 template <typename T>
 __global__ __launch_bounds__(256) void ingest_kernel(const T* __restrict__ src, int H0, int W0,

@@ -20,6 +20,10 @@ Same public names, constructor arguments and behaviour as the reference:
             with len() = number of batches, as torch DataLoaders of the reference's
             collated batches (callers' `data.to(device)` is then a no-op).
 
+Beyond the reference: raw detector patterns are background-corrected on the device by
+`correct_patterns(raw, image_size, PatternCorrection(...))` (static and dynamic background,
+per-pattern rescale; csrc/correct.hip), the ingest `index_scan(correction=...)` uses.
+
 Lightning is optional: DPDataModule subclasses `pl.LightningDataModule` when
 pytorch_lightning is importable.  There is no CPU fallback: the transform runs on the ROCm
 device or raises.  A user-supplied `transform` (any callable of the reference's kind) is
@@ -30,6 +34,7 @@ from __future__ import annotations
 import logging
 import math
 import threading
+from dataclasses import dataclass, field
 from pathlib import Path
 
 import numpy as np
@@ -100,6 +105,164 @@ def ingest_patterns_u8(raw, image_size=(128, 128), device="cuda", out: torch.Ten
     N.call("ebsdvae_ingest_patterns_u8", t.data_ptr(), B, H0, W0, h, w, N.ptr(out),
            N.stream(t.device))
     return out
+
+
+# ---------------------------------------------------------------- background correction
+_SRC_CODES = {torch.float64: 0, torch.float32: 1, torch.uint8: 2}   # src_dtype of the C entries
+_MODES = {"subtract": 1, "divide": 2}
+MAX_CORRECTED_SIDE = 256   # ebsdvae_correct_patterns' window limit per axis
+
+
+def gaussian_taps(sigma: float) -> tuple[np.ndarray, int]:
+    """One-sided taps of `scipy.ndimage.gaussian_filter(sigma, truncate=4.0)`: radius
+    r = int(4 sigma + 0.5) and exp(-i^2 / 2 sigma^2) / sum over -r..r for i = 0..r, computed in
+    float64 and rounded to float32.  Returns (taps (r + 1,) float32, r)."""
+    sigma = float(sigma)
+    if not (sigma > 0.0 and math.isfinite(sigma)):
+        raise ValueError(f"sigma must be a positive finite number, got {sigma}")
+    r = int(4.0 * sigma + 0.5)
+    x = np.arange(-r, r + 1, dtype=np.float64)
+    phi = np.exp(-0.5 / (sigma * sigma) * x ** 2)
+    phi /= phi.sum()
+    return phi[r:].astype(np.float32), r
+
+
+def _crop_offset(size: int, crop: int) -> int:
+    """Source offset of the centre crop along one axis (crop <= size): round((size - crop) / 2),
+    half to even, as torchvision's center_crop and csrc/crop.h."""
+    return int(round((size - crop) / 2.0))
+
+
+@dataclass(frozen=True, eq=False)
+class PatternCorrection:
+    """Background correction of raw detector patterns, applied by `correct_patterns` on the
+    cropped window: static background (subtract or divide by the (H0, W0) pattern
+    `static_background`, e.g. `DiffractionPatternIndexer.scan_background`), then dynamic
+    background (subtract or divide by the pattern's own Gaussian blur of `dynamic_sigma` pixels,
+    border "reflect", truncated at 4 sigma), then a rescale of every pattern to [0, 1].  A step
+    whose parameter is None is skipped; the rescale always runs."""
+
+    static_background: np.ndarray | None = None
+    static_mode: str = "subtract"
+    dynamic_sigma: float | None = None
+    dynamic_mode: str = "subtract"
+    # per device: the uploaded background and taps (filled by correct_patterns)
+    _device_state: dict = field(default_factory=dict, init=False, repr=False)
+
+    def __post_init__(self):
+        for name in ("static_mode", "dynamic_mode"):
+            if getattr(self, name) not in _MODES:
+                raise ValueError(f"{name} must be 'subtract' or 'divide', got {getattr(self, name)!r}")
+        if self.static_background is not None:
+            bg = np.array(self.static_background, dtype=np.float32, order="C")   # a private copy
+            if bg.ndim != 2:
+                raise ValueError(f"static_background must be a 2-D (H0, W0) pattern, got shape {bg.shape}")
+            if not np.isfinite(bg).all():
+                raise ValueError("static_background holds non-finite values")
+            bg.setflags(write=False)
+            object.__setattr__(self, "static_background", bg)
+        if self.dynamic_sigma is not None:
+            sigma = float(self.dynamic_sigma)
+            if not (sigma > 0.0 and math.isfinite(sigma)):
+                raise ValueError(f"dynamic_sigma must be a positive finite number, got {self.dynamic_sigma}")
+            object.__setattr__(self, "dynamic_sigma", sigma)
+
+    @property
+    def static_code(self) -> int:
+        return 0 if self.static_background is None else _MODES[self.static_mode]
+
+    @property
+    def dynamic_code(self) -> int:
+        return 0 if self.dynamic_sigma is None else _MODES[self.dynamic_mode]
+
+    def check(self, H0: int, W0: int, h: int, w: int) -> None:
+        """Everything that depends on the pattern and window sizes; raises ValueError."""
+        if h > H0 or w > W0:
+            raise ValueError(f"the ({h}, {w}) window does not fit ({H0}, {W0}) patterns "
+                             "(the corrected ingest crops, it does not pad)")
+        if not (0 < h <= MAX_CORRECTED_SIDE and 0 < w <= MAX_CORRECTED_SIDE):
+            raise ValueError(f"the window ({h}, {w}) must lie within "
+                             f"({MAX_CORRECTED_SIDE}, {MAX_CORRECTED_SIDE})")
+        bg = self.static_background
+        if bg is not None:
+            if bg.shape != (H0, W0):
+                raise ValueError(f"static_background is {bg.shape}, the patterns are ({H0}, {W0})")
+            if self.static_mode == "divide":
+                t, l = _crop_offset(H0, h), _crop_offset(W0, w)
+                if not (bg[t:t + h, l:l + w] > 0).all():
+                    raise ValueError("static_mode 'divide' needs a background that is positive "
+                                     "everywhere inside the cropped window")
+        if self.dynamic_sigma is not None:
+            r = int(4.0 * self.dynamic_sigma + 0.5)
+            if r > min(h, w):
+                raise ValueError(f"dynamic_sigma={self.dynamic_sigma} gives a blur radius of {r}, "
+                                 f"more than the window's smaller side {min(h, w)}")
+
+    def _on(self, device: torch.device):
+        """(background, taps, radius) on `device`, uploaded on first use."""
+        st = self._device_state.get(device)
+        if st is None:
+            bg = taps = None
+            r = 0
+            if self.static_background is not None:
+                bg = torch.from_numpy(self.static_background.copy()).to(device)   # ours is read-only
+            if self.dynamic_sigma is not None:
+                t, r = gaussian_taps(self.dynamic_sigma)
+                taps = torch.from_numpy(t).to(device)
+            st = self._device_state[device] = (bg, taps, r)
+        return st
+
+
+def correct_patterns(raw, image_size=(128, 128), correction: PatternCorrection | None = None,
+                     device="cuda", out: torch.Tensor | None = None):
+    """Background-corrected ingest on the device: raw (B, H0, W0) detector patterns (uint8,
+    float32 or float64, host or device) -> (B, 1, h, w) float32 in [0, 1]: centre crop (no
+    padding), `correction`'s static and dynamic steps, per-pattern rescale
+    (`ebsdvae_correct_patterns`, csrc/correct.hip).  Float sources are raw intensities of any
+    scale.  Shapes and sizes are checked before anything touches the device; the background and
+    the taps are uploaded once per (correction, device)."""
+    if not isinstance(correction, PatternCorrection):
+        raise TypeError(f"correction must be a PatternCorrection, got {type(correction).__name__}")
+    t = torch.as_tensor(raw)
+    if t.dtype not in _SRC_CODES:
+        raise TypeError(f"correct_patterns needs uint8, float32 or float64 patterns, got {t.dtype}")
+    if t.ndim == 2:
+        t = t.unsqueeze(0)
+    if t.ndim != 3:
+        raise ValueError(f"patterns must be (B, H, W), got {tuple(t.shape)}")
+    B, H0, W0 = t.shape
+    h, w = (int(v) for v in image_size)
+    correction.check(H0, W0, h, w)
+    if out is not None and (out.numel() != B * h * w or not out.is_contiguous()):
+        raise ValueError(f"out must be a contiguous ({B}, 1, {h}, {w}) tensor, got {tuple(out.shape)}")
+    t = t.to(device, non_blocking=True).contiguous()
+    if not t.is_cuda:
+        raise RuntimeError("correct_patterns needs a ROCm device (no CPU fallback)")
+    bg, taps, radius = correction._on(t.device)
+    if out is None:
+        out = torch.empty(B, 1, h, w, dtype=torch.float32, device=t.device)
+    nbytes = N.call("ebsdvae_correct_patterns_work", B, h, w)
+    work = torch.empty(nbytes, dtype=torch.uint8, device=t.device) if nbytes else None
+    N.call("ebsdvae_correct_patterns", t.data_ptr(), _SRC_CODES[t.dtype], B, H0, W0, h, w,
+           N.ptr(bg), correction.static_code, N.ptr(taps), radius, correction.dynamic_code,
+           N.ptr(out), work.data_ptr() if work is not None else None, N.stream(t.device))
+    return out
+
+
+def accumulate_patterns(raw: torch.Tensor, acc: torch.Tensor) -> torch.Tensor:
+    """acc (H0, W0) float64 += the sum over a device batch raw (B, H0, W0) (uint8, float32 or
+    float64), each pixel in batch order (`ebsdvae_accumulate_patterns`)."""
+    if raw.dtype not in _SRC_CODES:
+        raise TypeError(f"accumulate_patterns needs uint8, float32 or float64 patterns, got {raw.dtype}")
+    if raw.ndim != 3 or tuple(acc.shape) != tuple(raw.shape[1:]) or acc.dtype != torch.float64:
+        raise ValueError(f"patterns {tuple(raw.shape)} / accumulator {tuple(acc.shape)} {acc.dtype}: "
+                         "need (B, H0, W0) and a float64 (H0, W0)")
+    if not (raw.is_cuda and acc.is_cuda and raw.is_contiguous() and acc.is_contiguous()):
+        raise RuntimeError("accumulate_patterns needs contiguous tensors on a ROCm device")
+    B, H0, W0 = raw.shape
+    N.call("ebsdvae_accumulate_patterns", raw.data_ptr(), _SRC_CODES[raw.dtype], B, H0, W0,
+           acc.data_ptr(), N.stream(raw.device))
+    return acc
 
 
 class PatternTransform:

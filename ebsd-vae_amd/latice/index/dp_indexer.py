@@ -16,7 +16,9 @@ path: same `IndexerConfig` and `DiffractionPatternIndexer` API and call contract
 * `index_scan` has no counterpart in the reference: a whole scan (a .npy path, a host array of
   float or uint8 patterns, or a transformed device tensor) streams through pinned staging
   buffers, ingest, `encode_mu` and `db.index_latents`, and comes back as one
-  `ScanIndexResult` of numpy arrays (latice/index/scan.py).
+  `ScanIndexResult` of numpy arrays (latice/index/scan.py).  Raw detector scans take
+  `correction=PatternCorrection(...)`: the ingest is then `correct_patterns` (static and
+  dynamic background, rescale); `scan_background` streams a scan into its mean pattern.
 """
 from __future__ import annotations
 
@@ -29,7 +31,8 @@ import numpy as np
 import torch
 from pydantic.dataclasses import dataclass
 
-from latice.data_module import (DPDataModule, PatternTransform, create_default_transform,
+from latice.data_module import (DPDataModule, PatternCorrection, PatternTransform,
+                                accumulate_patterns, correct_patterns, create_default_transform,
                                 ingest_patterns, ingest_patterns_u8)
 from latice.index.faiss_db import (MAX_K, FaissLatentVectorDatabase,
                                    FaissLatentVectorDatabaseConfig, LatentIndexResult,
@@ -167,7 +170,8 @@ class DiffractionPatternIndexer:
     def index_scan(self, patterns, top_n: int | None = None,
                    orientation_threshold: float | None = None, min_required_matches: int = 18,
                    max_iterations: int = 3, batch_size: int | None = None,
-                   return_candidates: bool = False) -> ScanIndexResult:
+                   return_candidates: bool = False,
+                   correction: PatternCorrection | None = None) -> ScanIndexResult:
         """A whole scan in, an orientation map out, everything between on the device.
 
         `patterns` is a path to a .npy file (memory-mapped), a numpy array / memmap
@@ -177,7 +181,17 @@ class DiffractionPatternIndexer:
         staging buffers -> async copy on a copy stream -> ingest -> `model.encode_mu` ->
         `db.index_latents` into result arrays preallocated for all N patterns (44 B per
         pattern without candidates).  The host waits only for a staging buffer to be free
-        again, never for a batch's results; the results come back in one copy at the end."""
+        again, never for a batch's results; the results come back in one copy at the end.
+
+        With `correction` (a `PatternCorrection`) a host scan of raw detector patterns takes
+        the background-corrected ingest `correct_patterns` in place of the plain one, for
+        every staging dtype; a device tensor is already transformed and cannot take one."""
+        if correction is not None:
+            if not isinstance(correction, PatternCorrection):
+                raise TypeError(f"correction must be a PatternCorrection, got {type(correction).__name__}")
+            if torch.is_tensor(patterns):
+                raise ValueError("a tensor scan is already transformed: `correction` applies to "
+                                 "host scans of raw detector patterns")
         top_n = top_n or self.config.top_n
         orientation_threshold = orientation_threshold or self.config.orientation_threshold
         batch_size = int(batch_size or self.config.batch_size)
@@ -202,6 +216,8 @@ class DiffractionPatternIndexer:
         else:
             patterns = open_scan(patterns)
             items = scan_batches(patterns, batch_size)
+            if correction is not None:
+                correction.check(*patterns.shape[1:], *self.config.image_size)
             n, dev = patterns.shape[0], self.device
         k = min(top_n, self.db.get_count()) if return_candidates else 0
 
@@ -231,7 +247,7 @@ class DiffractionPatternIndexer:
                 e = min(s + batch_size, n)
                 self.db.index_latents(self.model.encode_mu(patterns[s:e]), out=res.slice(s, e), **kw)
         elif n:
-            staging = self._stream_scan(patterns, items, batch_size, dev, res, kw)
+            staging = self._stream_scan(patterns, items, batch_size, dev, res, kw, correction)
 
         host = buf.cpu().numpy()     # the one device-to-host copy (and the only host wait)
         del staging                  # every copy-stream buffer outlived its last consumer
@@ -243,25 +259,49 @@ class DiffractionPatternIndexer:
                                candidate_indices=h.get("cand_idx"),
                                candidate_scores=h.get("cand_scores"))
 
-    def _stream_scan(self, patterns, items, batch_size, dev, res, kw):
-        """The host half of index_scan: batch i is copied from the scan into pinned buffer
+    def _stream_scan(self, patterns, items, batch_size, dev, res, kw, correction=None):
+        """index_scan over a host scan: every staged batch is ingested into one (B, 1, h, w)
+        buffer (the corrected ingest with a `correction`, else the plain one of the staging
+        dtype), then encoded and indexed into its rows of `res`."""
+        code = items[0][2]
+        h, w = self.config.image_size
+        with torch.cuda.device(dev):
+            x = torch.empty(min(batch_size, patterns.shape[0]), 1, h, w, dtype=torch.float32,
+                            device=dev)
+
+        def ingest(raw):
+            out = x[:raw.shape[0]]
+            if correction is not None:
+                correct_patterns(raw, (h, w), correction, dev, out=out)
+            elif code == SCAN_U8:
+                ingest_patterns_u8(raw, (h, w), dev, out=out)
+            else:
+                ingest_patterns(raw, (h, w), dev, out=out)
+
+        def index(s, e):
+            self.db.index_latents(self.model.encode_mu(x[:e - s]), out=res.slice(s, e), **kw)
+
+        return self._stream_batches(patterns, items, batch_size, dev, ingest, index) + (x,)
+
+    def _stream_batches(self, patterns, items, batch_size, dev, ingest, then=None):
+        """The host half of a streamed scan: batch i is copied from the scan into pinned buffer
         i & 1, then to device buffer i & 1 on a copy stream, while the compute stream still
-        works on batch i - 1.  Events order the two streams in both directions; the host
-        waits only for `copied[j]` (the copy out of the pinned buffer it is about to refill).
-        The staging buffers are returned: the caller keeps them alive until its result copy
-        has synchronised the compute stream, which has waited for every copy."""
+        works on batch i - 1; `ingest(staged batch)` is the one consumer of the device buffer,
+        `then(start, stop)` whatever follows it on the compute stream.  Events order the two
+        streams in both directions; the host waits only for `copied[j]` (the copy out of the
+        pinned buffer it is about to refill).  The staging buffers are returned: the caller
+        keeps them alive until it has synchronised the compute stream, which has waited for
+        every copy."""
         per = tuple(patterns.shape[1:])
         code = items[0][2]
         th_dt = {SCAN_F64: torch.float64, SCAN_F32: torch.float32, SCAN_U8: torch.uint8}[code]
         shape = (min(batch_size, patterns.shape[0]),) + per
-        h, w = self.config.image_size
         with torch.cuda.device(dev):
             compute = torch.cuda.current_stream(dev)
             copy = torch.cuda.Stream(dev)
             pinned = [torch.empty(shape, dtype=th_dt).pin_memory() for _ in range(2)]
             pinned_np = [p.numpy() for p in pinned]
             staged = [torch.empty(shape, dtype=th_dt, device=dev) for _ in range(2)]
-            x = torch.empty(shape[0], 1, h, w, dtype=torch.float32, device=dev)
             # the allocator may hand out blocks with work still pending on the compute stream
             begun = torch.cuda.Event()
             begun.record(compute)
@@ -280,14 +320,31 @@ class DiffractionPatternIndexer:
                 copied[j] = torch.cuda.Event()
                 copied[j].record(copy)
                 compute.wait_event(copied[j])
-                if code == SCAN_U8:
-                    ingest_patterns_u8(staged[j][:m], (h, w), dev, out=x[:m])
-                else:
-                    ingest_patterns(staged[j][:m], (h, w), dev, out=x[:m])
+                ingest(staged[j][:m])
                 ingested[j] = torch.cuda.Event()
                 ingested[j].record(compute)
-                self.db.index_latents(self.model.encode_mu(x[:m]), out=res.slice(s, e), **kw)
-        return pinned, staged, x
+                if then is not None:
+                    then(s, e)
+        return pinned, staged
+
+    def scan_background(self, patterns, batch_size: int | None = None) -> np.ndarray:
+        """The mean pattern of a scan, the usual static background: `patterns` (a .npy path or a
+        host array (N, H0, W0)) streams through the staging buffers of index_scan into a
+        float64 running sum on the device (`ebsdvae_accumulate_patterns`).  Returns the
+        (H0, W0) float32 pattern float32(sum / N), the division in float64."""
+        batch_size = int(batch_size or self.config.batch_size)
+        patterns = open_scan(patterns)
+        items = scan_batches(patterns, batch_size)
+        if not items:
+            raise ValueError("scan_background needs at least one pattern")
+        if self.device.type != "cuda":
+            raise RuntimeError("scan_background needs a ROCm device (no CPU fallback)")
+        acc = torch.zeros(tuple(patterns.shape[1:]), dtype=torch.float64, device=self.device)
+        staging = self._stream_batches(patterns, items, batch_size, self.device,
+                                       lambda raw: accumulate_patterns(raw, acc))
+        total = acc.cpu().numpy()    # the host's one wait: every batch has been added
+        del staging
+        return (total / patterns.shape[0]).astype(np.float32)
 
     @cached_property
     def _create_dataloader(self):

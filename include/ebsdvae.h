@@ -536,6 +536,31 @@ int ebsdvae_ingest_patterns(const void* src, int src_dtype, int B, int H0, int W
 int ebsdvae_ingest_patterns_u8(const unsigned char* src, int B, int H0, int W0, int out_h,
                                int out_w, float* dst, ebsdvae_stream_t stream);
 
+/* ---- background-corrected ingest ("Pattern correction") ----------
+ * Raw detector patterns (B, H0, W0) (src_dtype 0 = float64, 1 = float32, 2 = uint8) ->
+ * dst (B, 1, out_h, out_w) in [0, 1].  Per pattern, on the centre-cropped window (the crop
+ * offsets of ebsdvae_ingest_patterns; no padding: H0 >= out_h, W0 >= out_w; out_h, out_w <= 256):
+ *   v = float32(src), non-finite -> 0;
+ *   s = v (static_mode 0), v - bg (1) or v / bg (2), static_bg the (H0, W0) background;
+ *   b = Gaussian blur of s, separable, x then y, border "reflect": taps[0 .. radius] are the
+ *       one-sided normalised taps, radius <= min(out_h, out_w);
+ *   d = s (dynamic_mode 0), s - b (1) or s / b with 0 where b == 0 (2);
+ *   out = (d - min d) / (max d - min d), 0 everywhere when max == min.
+ * static_bg is NULL iff static_mode is 0, taps NULL iff dynamic_mode is 0.  Windows of up to
+ * 128 x 128 pixels run as one launch and need no scratch; larger ones run in phases through
+ * work, device scratch of ebsdvae_correct_patterns_work(B, out_h, out_w) bytes (0 when none is
+ * needed).  The values are the same on both paths, and a pattern's output does not depend on
+ * the other patterns of the call. */
+int ebsdvae_correct_patterns(const void* src, int src_dtype, int B, int H0, int W0, int out_h,
+                             int out_w, const float* static_bg, int static_mode,
+                             const float* taps, int radius, int dynamic_mode, float* dst,
+                             void* work, ebsdvae_stream_t stream);
+size_t ebsdvae_correct_patterns_work(int B, int out_h, int out_w);
+/* acc[y][x] += sum over the batch, in batch order, of float64(src[b][y][x]) at detector size
+ * (H0, W0): the running sum behind a scan-mean background.  Exact for uint8 sources. */
+int ebsdvae_accumulate_patterns(const void* src, int src_dtype, int B, int H0, int W0,
+                                double* acc, ebsdvae_stream_t stream);
+
 /* ---- whole-scan indexing: search + consensus in one call ------------------------------
  * ebsdvae_cosine_topk followed by ebsdvae_orient_consensus without the launch boundary
  * between them: the wave that merges a query's top-k list (candidate l in lane l) loads
