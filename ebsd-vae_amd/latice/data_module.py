@@ -22,7 +22,10 @@ Same public names, constructor arguments and behaviour as the reference:
 
 Beyond the reference: raw detector patterns are background-corrected on the device by
 `correct_patterns(raw, image_size, PatternCorrection(...))` (static and dynamic background,
-per-pattern rescale; csrc/correct.hip), the ingest `index_scan(correction=...)` uses.
+per-pattern rescale; csrc/correct.hip), the ingest `index_scan(correction=...)` uses, and
+transformed patterns are averaged with their neighbours on the scan grid by
+`average_neighbour_patterns(x, NeighbourAverage(...))` (csrc/neighbour.hip), the stage
+`index_scan(neighbour_average=...)` puts between ingest and encoder.
 
 Lightning is optional: DPDataModule subclasses `pl.LightningDataModule` when
 pytorch_lightning is importable.  There is no CPU fallback: the transform runs on the ROCm
@@ -263,6 +266,152 @@ def accumulate_patterns(raw: torch.Tensor, acc: torch.Tensor) -> torch.Tensor:
     N.call("ebsdvae_accumulate_patterns", raw.data_ptr(), _SRC_CODES[raw.dtype], B, H0, W0,
            acc.data_ptr(), N.stream(raw.device))
     return acc
+
+
+# ---------------------------------------------------------------- neighbour pattern averaging
+MAX_NEIGHBOUR_SIDE = 5   # ebsdvae_average_neighbours' window limit per axis
+_WINDOWS = ("rectangular", "circular", "gaussian")
+
+
+def neighbour_window(window: str = "circular", window_shape=(3, 3), std: float = 1.0) -> np.ndarray:
+    """A named averaging window of odd shape (2 hr + 1, 2 hc + 1), at most 5 x 5, built in
+    float64 over the offsets (a, b) from the centre and rounded to float32: "rectangular" all
+    ones, "circular" 1 where a^2 + b^2 <= max(hr, hc)^2 (3 x 3: the five-point cross), "gaussian"
+    exp(-(a^2 + b^2) / (2 std^2))."""
+    if window not in _WINDOWS:
+        raise ValueError(f"window must be one of {_WINDOWS}, got {window!r}")
+    try:
+        ny, nx = (int(v) for v in window_shape)
+    except (TypeError, ValueError):
+        raise ValueError(f"window_shape must be two integers, got {window_shape!r}") from None
+    for v in (ny, nx):
+        if not (1 <= v <= MAX_NEIGHBOUR_SIDE and v % 2 == 1):
+            raise ValueError(f"window_shape {window_shape!r}: sides must be odd and at most "
+                             f"{MAX_NEIGHBOUR_SIDE}")
+    std = float(std)
+    if not (std > 0.0 and math.isfinite(std)):
+        raise ValueError(f"std must be a positive finite number, got {std}")
+    hr, hc = ny // 2, nx // 2
+    a, b = np.mgrid[-hr:hr + 1, -hc:hc + 1].astype(np.float64)
+    r2 = a * a + b * b
+    if window == "rectangular":
+        wt = np.ones_like(r2)
+    elif window == "circular":
+        wt = (r2 <= float(max(hr, hc)) ** 2).astype(np.float64)
+    else:
+        wt = np.exp(-r2 / (2.0 * std * std))
+    return wt.astype(np.float32)
+
+
+@dataclass(frozen=True, eq=False)
+class NeighbourAverage:
+    """Averaging of every transformed pattern with its neighbours on the scan grid
+    (kikuchipy's `average_neighbour_patterns`), applied by `average_neighbour_patterns` and
+    `index_scan(neighbour_average=...)`.  The scan's N = rows * cols patterns lie on the grid
+    `scan_shape` = (rows, cols) in row-major order.  The window is the named one
+    (`neighbour_window(window, window_shape, std)`) unless `weights`, an explicit odd-sided array
+    of at most 5 x 5 finite non-negative weights with a positive centre, is given.  Neighbours
+    off the grid are dropped and the remaining weights renormalise; the result is not rescaled."""
+
+    scan_shape: tuple
+    window: str = "circular"
+    window_shape: tuple = (3, 3)
+    std: float = 1.0
+    weights: np.ndarray | None = None
+    # per device: the uploaded weights (filled on first use)
+    _device_state: dict = field(default_factory=dict, init=False, repr=False)
+
+    def __post_init__(self):
+        try:
+            rows, cols = (int(v) for v in self.scan_shape)
+        except (TypeError, ValueError):
+            raise ValueError(f"scan_shape must be (rows, cols), got {self.scan_shape!r}") from None
+        if rows < 1 or cols < 1 or rows * cols >= 1 << 31:
+            raise ValueError(f"scan_shape {self.scan_shape!r}: rows and cols must be positive "
+                             "(and rows * cols below 2^31)")
+        object.__setattr__(self, "scan_shape", (rows, cols))
+        if self.weights is None:
+            wt = neighbour_window(self.window, self.window_shape, self.std)
+        else:
+            wt = np.array(self.weights, dtype=np.float32, order="C")   # a private copy
+            if wt.ndim != 2 or any(s % 2 == 0 or s > MAX_NEIGHBOUR_SIDE for s in wt.shape):
+                raise ValueError(f"weights must be 2-D with odd sides of at most "
+                                 f"{MAX_NEIGHBOUR_SIDE}, got shape {wt.shape}")
+            if not np.isfinite(wt).all() or (wt < 0).any():
+                raise ValueError("weights must be finite and non-negative")
+        if not wt[wt.shape[0] // 2, wt.shape[1] // 2] > 0:
+            raise ValueError("the centre weight must be positive")
+        wt.setflags(write=False)
+        object.__setattr__(self, "weights", wt)
+        object.__setattr__(self, "window_shape", tuple(wt.shape))
+
+    @property
+    def half(self) -> tuple[int, int]:
+        """(hr, hc): the window reaches hr scan rows and hc scan columns each way."""
+        return self.weights.shape[0] // 2, self.weights.shape[1] // 2
+
+    @property
+    def reach(self) -> int:
+        """hr * cols + hc: how far, in flat scan index, a pattern's neighbours lie from it."""
+        hr, hc = self.half
+        return hr * self.scan_shape[1] + hc
+
+    def check(self, n: int) -> None:
+        rows, cols = self.scan_shape
+        if int(n) != rows * cols:
+            raise ValueError(f"the scan has {n} patterns, scan_shape {self.scan_shape} needs "
+                             f"{rows * cols}")
+
+    def _on(self, device: torch.device) -> torch.Tensor:
+        """The weights on `device`, uploaded on first use."""
+        wt = self._device_state.get(device)
+        if wt is None:
+            wt = self._device_state[device] = torch.from_numpy(self.weights.copy()).to(device)
+        return wt
+
+
+def average_neighbour_range(ring: torch.Tensor, neighbour_average: NeighbourAverage, p0: int,
+                            count: int, out: torch.Tensor) -> torch.Tensor:
+    """out[:count] = the averaged patterns [p0, p0 + count) of the scan (`ebsdvae_average_neighbours`,
+    csrc/neighbour.hip).  `ring` (cap, 1, h, w) float32 holds scan pattern q in slot q % cap and
+    every on-grid neighbour of the range is resident; a resident scan is its own ring (cap = N).
+    `out` is contiguous, holds at least `count` patterns and does not overlap `ring`."""
+    if not (ring.is_cuda and ring.dtype == torch.float32 and ring.dim() == 4 and ring.shape[1] == 1
+            and ring.is_contiguous()):
+        raise RuntimeError("average_neighbour_range needs a contiguous (cap, 1, h, w) float32 "
+                           "tensor on a ROCm device (no CPU fallback)")
+    cap, _, h, w = ring.shape
+    if not (out.is_cuda and out.is_contiguous() and out.dtype == torch.float32
+            and out.numel() >= count * h * w):
+        raise ValueError(f"out must be a contiguous float32 device tensor of at least {count} "
+                         f"({h}, {w}) patterns, got {tuple(out.shape)}")
+    hr, hc = neighbour_average.half
+    rows, cols = neighbour_average.scan_shape
+    N.call("ebsdvae_average_neighbours", N.ptr(ring), cap, rows, cols, int(p0), int(count),
+           N.ptr(neighbour_average._on(ring.device)), hr, hc, h, w, N.ptr(out),
+           N.stream(ring.device))
+    return out
+
+
+def average_neighbour_patterns(x: torch.Tensor, neighbour_average: NeighbourAverage,
+                               out: torch.Tensor | None = None) -> torch.Tensor:
+    """A resident scan of transformed patterns x (N, 1, h, w) float32 on the device (what
+    `ingest_patterns`, `ingest_patterns_u8` or `correct_patterns` wrote) -> a new tensor of that
+    shape in which every pattern is averaged with its neighbours on the scan grid."""
+    if not isinstance(neighbour_average, NeighbourAverage):
+        raise TypeError("neighbour_average must be a NeighbourAverage, got "
+                        f"{type(neighbour_average).__name__}")
+    if not torch.is_tensor(x) or not x.is_cuda:
+        raise RuntimeError("average_neighbour_patterns needs a tensor on a ROCm device "
+                           "(no CPU fallback)")
+    if x.dim() != 4 or x.shape[1] != 1 or x.dtype != torch.float32:
+        raise ValueError(f"patterns must be (N, 1, h, w) float32, got {tuple(x.shape)} {x.dtype}")
+    neighbour_average.check(x.shape[0])
+    if out is None:
+        out = torch.empty_like(x, memory_format=torch.contiguous_format)
+    elif out.shape != x.shape:
+        raise ValueError(f"out must be a {tuple(x.shape)} tensor, got {tuple(out.shape)}")
+    return average_neighbour_range(x.contiguous(), neighbour_average, 0, x.shape[0], out)
 
 
 class PatternTransform:

@@ -19,6 +19,9 @@ path: same `IndexerConfig` and `DiffractionPatternIndexer` API and call contract
   `ScanIndexResult` of numpy arrays (latice/index/scan.py).  Raw detector scans take
   `correction=PatternCorrection(...)`: the ingest is then `correct_patterns` (static and
   dynamic background, rescale); `scan_background` streams a scan into its mean pattern.
+  `neighbour_average=NeighbourAverage(...)` averages every transformed pattern with its
+  neighbours on the scan grid between ingest and encoder; a host scan then streams through a
+  device ring of transformed patterns (latice/index/scan.py `neighbour_schedule`).
 """
 from __future__ import annotations
 
@@ -31,14 +34,15 @@ import numpy as np
 import torch
 from pydantic.dataclasses import dataclass
 
-from latice.data_module import (DPDataModule, PatternCorrection, PatternTransform,
-                                accumulate_patterns, correct_patterns, create_default_transform,
-                                ingest_patterns, ingest_patterns_u8)
+from latice.data_module import (DPDataModule, NeighbourAverage, PatternCorrection,
+                                PatternTransform, accumulate_patterns, average_neighbour_range,
+                                correct_patterns, create_default_transform, ingest_patterns,
+                                ingest_patterns_u8)
 from latice.index.faiss_db import (MAX_K, FaissLatentVectorDatabase,
                                    FaissLatentVectorDatabaseConfig, LatentIndexResult,
                                    OrientationResult)
-from latice.index.scan import (SCAN_F32, SCAN_F64, SCAN_U8, ScanIndexResult, open_scan,
-                               scan_batches)
+from latice.index.scan import (SCAN_F32, SCAN_F64, SCAN_U8, ScanIndexResult, neighbour_schedule,
+                               open_scan, scan_batches)
 from latice.model import VariationalAutoEncoder
 
 logger = logging.getLogger(__name__)
@@ -76,6 +80,17 @@ def _default_db(dimension: int, device: torch.device):
         return FaissLatentVectorDatabase(
             FaissLatentVectorDatabaseConfig(dimension=dimension, device=str(device)))
     return ChromaLatentVectorDatabase(dimension=dimension)
+
+
+def _ingest_staged(raw, out, code, correction, size, dev):
+    """One staged batch of a host scan -> transformed patterns in `out`: the corrected ingest
+    with a `correction`, else the plain one of the staging dtype `code`."""
+    if correction is not None:
+        correct_patterns(raw, size, correction, dev, out=out)
+    elif code == SCAN_U8:
+        ingest_patterns_u8(raw, size, dev, out=out)
+    else:
+        ingest_patterns(raw, size, dev, out=out)
 
 
 class DiffractionPatternIndexer:
@@ -171,7 +186,8 @@ class DiffractionPatternIndexer:
                    orientation_threshold: float | None = None, min_required_matches: int = 18,
                    max_iterations: int = 3, batch_size: int | None = None,
                    return_candidates: bool = False,
-                   correction: PatternCorrection | None = None) -> ScanIndexResult:
+                   correction: PatternCorrection | None = None,
+                   neighbour_average: NeighbourAverage | None = None) -> ScanIndexResult:
         """A whole scan in, an orientation map out, everything between on the device.
 
         `patterns` is a path to a .npy file (memory-mapped), a numpy array / memmap
@@ -185,7 +201,18 @@ class DiffractionPatternIndexer:
 
         With `correction` (a `PatternCorrection`) a host scan of raw detector patterns takes
         the background-corrected ingest `correct_patterns` in place of the plain one, for
-        every staging dtype; a device tensor is already transformed and cannot take one."""
+        every staging dtype; a device tensor is already transformed and cannot take one.
+
+        With `neighbour_average` (a `NeighbourAverage` whose scan_shape holds the N patterns)
+        every transformed pattern is averaged with its neighbours on the scan grid before the
+        encoder reads it: ingest or correction, then averaging, then encoder.  It acts on
+        transformed patterns, so a device tensor may take it too.  A host scan is ingested, each
+        pattern once, into a device ring of batch_size + 2 (hr cols + hc) transformed patterns;
+        the outputs whose neighbours have all arrived are averaged straight into the encoder's
+        batch buffer, in chunks of at most batch_size."""
+        if neighbour_average is not None and not isinstance(neighbour_average, NeighbourAverage):
+            raise TypeError("neighbour_average must be a NeighbourAverage, got "
+                            f"{type(neighbour_average).__name__}")
         if correction is not None:
             if not isinstance(correction, PatternCorrection):
                 raise TypeError(f"correction must be a PatternCorrection, got {type(correction).__name__}")
@@ -219,6 +246,8 @@ class DiffractionPatternIndexer:
             if correction is not None:
                 correction.check(*patterns.shape[1:], *self.config.image_size)
             n, dev = patterns.shape[0], self.device
+        if neighbour_average is not None:
+            neighbour_average.check(n)
         k = min(top_n, self.db.get_count()) if return_candidates else 0
 
         # every result array is a view of ONE device buffer, so one copy brings them all
@@ -242,10 +271,23 @@ class DiffractionPatternIndexer:
         staging = None
         res = LatentIndexResult(**carve(buf, lambda b, dt, shape: b.view(dt).view(shape)))
 
-        if on_device:
+        if on_device and neighbour_average is not None and n:
+            ring = patterns.contiguous()     # a resident scan is its own ring
+            with torch.cuda.device(dev):
+                x = torch.empty((min(batch_size, n),) + tuple(ring.shape[1:]),
+                                dtype=torch.float32, device=dev)
+            for s in range(0, n, batch_size):
+                e = min(s + batch_size, n)
+                average_neighbour_range(ring, neighbour_average, s, e - s, x)
+                self.db.index_latents(self.model.encode_mu(x[:e - s]), out=res.slice(s, e), **kw)
+            staging = (ring, x)
+        elif on_device:
             for s in range(0, n, batch_size):
                 e = min(s + batch_size, n)
                 self.db.index_latents(self.model.encode_mu(patterns[s:e]), out=res.slice(s, e), **kw)
+        elif n and neighbour_average is not None:
+            staging = self._stream_scan_averaged(patterns, items, batch_size, dev, res, kw,
+                                                 correction, neighbour_average)
         elif n:
             staging = self._stream_scan(patterns, items, batch_size, dev, res, kw, correction)
 
@@ -270,18 +312,47 @@ class DiffractionPatternIndexer:
                             device=dev)
 
         def ingest(raw):
-            out = x[:raw.shape[0]]
-            if correction is not None:
-                correct_patterns(raw, (h, w), correction, dev, out=out)
-            elif code == SCAN_U8:
-                ingest_patterns_u8(raw, (h, w), dev, out=out)
-            else:
-                ingest_patterns(raw, (h, w), dev, out=out)
+            _ingest_staged(raw, x[:raw.shape[0]], code, correction, (h, w), dev)
 
         def index(s, e):
             self.db.index_latents(self.model.encode_mu(x[:e - s]), out=res.slice(s, e), **kw)
 
         return self._stream_batches(patterns, items, batch_size, dev, ingest, index) + (x,)
+
+    def _stream_scan_averaged(self, patterns, items, batch_size, dev, res, kw, correction,
+                              neighbour_average):
+        """index_scan over a host scan with neighbour averaging: every staged batch is ingested,
+        once, into its slots of a ring of transformed patterns (`neighbour_schedule`; in two
+        parts where it passes the ring's end); the outputs that are complete after it are
+        averaged from the ring into the encoder's batch buffer, chunk by chunk, then encoded and
+        indexed into their rows of `res`.  All of it is work on the compute stream, in order:
+        the ring is overwritten only after the last averaging that reads the old patterns."""
+        code = items[0][2]
+        h, w = self.config.image_size
+        n = patterns.shape[0]
+        hr, hc = neighbour_average.half
+        schedule = neighbour_schedule(n, neighbour_average.scan_shape[1], hr, hc, batch_size)
+        with torch.cuda.device(dev):
+            ring = torch.empty(schedule.ring_cap, 1, h, w, dtype=torch.float32, device=dev)
+            x = torch.empty(min(batch_size, n), 1, h, w, dtype=torch.float32, device=dev)
+        steps = iter(schedule.steps)    # one per staged batch, in the order of `items`
+        current = []
+
+        def ingest(raw):
+            step = next(steps)
+            current[:] = [step]
+            for a, b, slot in step.ingest:
+                _ingest_staged(raw[a - step.start:b - step.start], ring[slot:slot + b - a], code,
+                               correction, (h, w), dev)
+
+        def index(s, e):
+            step, = current
+            assert (step.start, step.stop) == (s, e)
+            for a, b in step.ready:
+                average_neighbour_range(ring, neighbour_average, a, b - a, x)
+                self.db.index_latents(self.model.encode_mu(x[:b - a]), out=res.slice(a, b), **kw)
+
+        return self._stream_batches(patterns, items, batch_size, dev, ingest, index) + (ring, x)
 
     def _stream_batches(self, patterns, items, batch_size, dev, ingest, then=None):
         """The host half of a streamed scan: batch i is copied from the scan into pinned buffer

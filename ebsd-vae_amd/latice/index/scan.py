@@ -1,5 +1,6 @@
-"""Host side of `DiffractionPatternIndexer.index_scan`: the result record and the batching of
-a scan into work items.  numpy only: nothing here touches the device or the HIP library.
+"""Host side of `DiffractionPatternIndexer.index_scan`: the result record, the batching of
+a scan into work items and the schedule of a neighbour-averaged scan through its device ring.
+numpy only: nothing here touches the device or the HIP library.
 """
 from __future__ import annotations
 
@@ -63,3 +64,50 @@ def scan_batches(source: np.ndarray, batch_size: int) -> list[tuple[int, int, in
     code = scan_dtype_code(source.dtype)
     n = source.shape[0]
     return [(s, min(s + batch_size, n), code) for s in range(0, n, batch_size)]
+
+
+@dataclass(frozen=True)
+class NeighbourStep:
+    """One staged batch of a neighbour-averaged scan."""
+    start: int                  # the batch: flat scan range [start, stop)
+    stop: int
+    ingest: tuple               # ((start, stop, slot), ...): sub-ranges and the ring slot each begins at
+    ready: tuple                # ((start, stop), ...): output chunks that are complete after it
+
+
+@dataclass(frozen=True)
+class NeighbourSchedule:
+    ring_cap: int               # patterns in the ring; scan pattern q lives in slot q % ring_cap
+    steps: tuple
+
+
+def neighbour_schedule(n: int, cols: int, hr: int, hc: int, batch_size: int) -> NeighbourSchedule:
+    """How a host scan of n patterns on a grid of `cols` columns streams through a device ring
+    of transformed patterns when each is averaged over a (2 hr + 1) x (2 hc + 1) window.
+
+    A pattern's neighbours lie within reach = hr * cols + hc of its flat index.  The batches are
+    those of `scan_batches`.  After the batch ending at e has been ingested, the outputs below
+    e - reach are complete (all of them at e = n); they become ready in chunks of at most
+    `batch_size`.  A ready chunk [a, b) reads the patterns [a - reach, b + reach) of the scan,
+    the oldest of which is reach below the first output still to come, itself at most reach
+    below the batch's start: a ring of batch_size + 2 reach slots (or n, if that is less) holds
+    every pattern until its last reader has run.  A batch that passes the ring's end is
+    ingested in two parts; every pattern is ingested once."""
+    n, cols, hr, hc, batch_size = int(n), int(cols), int(hr), int(hc), int(batch_size)
+    if n < 0 or cols < 1 or hr < 0 or hc < 0 or batch_size < 1:
+        raise ValueError(f"neighbour_schedule: n={n} cols={cols} hr={hr} hc={hc} batch_size={batch_size}")
+    reach = hr * cols + hc
+    cap = max(1, min(n, batch_size + 2 * reach))
+    steps, done = [], 0
+    for s in range(0, n, batch_size):
+        e = min(s + batch_size, n)
+        slot = s % cap
+        head = min(e - s, cap - slot)
+        ingest = [(s, s + head, slot)]
+        if s + head < e:
+            ingest.append((s + head, e, 0))
+        upto = n if e == n else max(done, e - reach)
+        ready = [(a, min(a + batch_size, upto)) for a in range(done, upto, batch_size)]
+        done = upto
+        steps.append(NeighbourStep(s, e, tuple(ingest), tuple(ready)))
+    return NeighbourSchedule(cap, tuple(steps))

@@ -561,6 +561,25 @@ size_t ebsdvae_correct_patterns_work(int B, int out_h, int out_w);
 int ebsdvae_accumulate_patterns(const void* src, int src_dtype, int B, int H0, int W0,
                                 double* acc, ebsdvae_stream_t stream);
 
+/* ---- neighbour pattern averaging ("Neighbour pattern averaging") --
+ * The scan's rows * cols transformed patterns T (h x w float32 each, values in [0, 1], what the
+ * ingests above write) lie on a grid in row-major order, pattern p at (i, j) = (p / cols,
+ * p % cols).  For p in [p0, p0 + count), dst[p - p0] =
+ *   sum W[a + hr][b + hc] * T[(i + a) cols + (j + b)]  /  sum W[a + hr][b + hc]
+ * over -hr <= a <= hr, -hc <= b <= hc with W != 0 and (i + a, j + b) on the grid: neighbours off
+ * the grid are dropped and the remaining weights renormalise.  Both sums are float32 fma chains
+ * from 0, a ascending then b ascending, and one true division ends them, so a pattern's output
+ * is a function of T, W and the grid alone (not of p0, count or ring_cap).
+ * src is a ring of ring_cap patterns: scan pattern q lives in slot q % ring_cap, and every
+ * on-grid neighbour of the range is resident (a resident scan: ring_cap = rows * cols).
+ * weights: the (2 hr + 1) x (2 hc + 1) window W on the device, finite and >= 0, centre > 0;
+ * hr, hc in 0..2.  dst: count contiguous patterns that do not overlap src.  h * w % 4 == 0.
+ * Nonzero for hr / hc out of range, a null pointer, count < 0 or a range that leaves the grid,
+ * h * w % 4 != 0, or ring_cap < min(rows * cols, count + 2 (hr cols + hc)).  No scratch. */
+int ebsdvae_average_neighbours(const float* src, long long ring_cap, int rows, int cols,
+                               long long p0, long long count, const float* weights, int hr,
+                               int hc, int h, int w, float* dst, ebsdvae_stream_t stream);
+
 /* ---- whole-scan indexing: search + consensus in one call ------------------------------
  * ebsdvae_cosine_topk followed by ebsdvae_orient_consensus without the launch boundary
  * between them: the wave that merges a query's top-k list (candidate l in lane l) loads
