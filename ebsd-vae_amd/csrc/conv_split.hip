@@ -1372,9 +1372,12 @@ static bool plan_split(int H, int W, int cin, int cout, int np, X3Cfg* c) {
   // pipelined kernel: interior columns only; the non-persistent kernel stages whole halo rows
   c->KX = use_pipe() ? ((c->TH + 2) * W * 2 + tpg - 1) / tpg : (pixI * 2 + tpg - 1) / tpg;
   // the item count each dispatch_split instantiation is compiled for
-  const int kxmax = np == 2 ? (cout == 128 ? 2 : (cout == 64 ? 5 : 7))
-                            : (np == NP_F16 ? (cout == 128 ? 2 : (cout == 64 ? 3 : 4))
-                                            : (cout == 128 ? 2 : (cout == 64 ? 4 : 5)));
+  // (the 64-pixel-map configurations are compiled for one item per thread, which covers 8x8,
+  // 4x16 and 16x4; a 1x64 map would need two and is refused here)
+  const int kxmax = H * W < 256 ? 1
+                    : np == 2 ? (cout == 128 ? 2 : (cout == 64 ? 5 : 7))
+                              : (np == NP_F16 ? (cout == 128 ? 2 : (cout == 64 ? 3 : 4))
+                                              : (cout == 128 ? 2 : (cout == 64 ? 4 : 5)));
   if (c->KX > kxmax) return false;
   const int wslab = XTAPS * npc(np) * cout * 16;
   c->lds = 2 * (size_t)wslab + 2 * (size_t)(pix + 1) * XPS;

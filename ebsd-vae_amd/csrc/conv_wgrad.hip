@@ -1446,6 +1446,11 @@ extern "C" int ebsdvae_conv3x3_wgrad_f16(const float* src, const float* src_stat
 extern "C" int ebsdvae_conv3x3_wgrad_slices(int B, int H, int W, int cin, int cout) {
   WgGeom g;
   if (!wg_geom(B, H, W, cin, cout, &g)) return -1;
+  // the MFMA kernel's three tile shapes (the cin = 1 and cout = 1 kernels take any tile):
+  // what ebsdvae_conv3x3_wgrad refuses, e.g. W = 8 with H >= 16, has no slice count
+  if (cin != 1 && cout != 1 &&
+      (cin % 32 || !(cout == 32 || cout % 64 == 0) || !wgs_geom_ok(g, WG_PT)))
+    return -1;
   return g.slices;
 }
 

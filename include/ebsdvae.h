@@ -243,7 +243,10 @@ int ebsdvae_conv3x3_dgrad_inbwd_f16_bst(const float* g, const float* gmax, int g
  * the slices in fixed order into the parameter-gradient layout of `kind` (0 conv,
  * 1 convT).  Replaces autograd's convolution_backward weight/bias outputs.
  * gy is the conv-output gradient (NHWC, cout channels); src/act as in the forward, except
- * that max-pool-fed layers pass their materialised pooled activation as RAW. */
+ * that max-pool-fed layers pass their materialised pooled activation as RAW.
+ * ebsdvae_conv3x3_wgrad_slices: the slice count, or -1 for a shape ebsdvae_conv3x3_wgrad
+ * refuses (128-pixel tiles of 4 x 32, 8 x 16 or two 8 x 8 images: W = 8 needs H = 8; the
+ * cin = 1 and cout = 1 kernels take any power-of-two tile). */
 int ebsdvae_conv3x3_wgrad_slices(int B, int H, int W, int cin, int cout);
 int ebsdvae_conv3x3_wgrad(const float* src, const float* src_stats, int src_mode,
                           const float* gy, float* wpart, float* bpart, int B, int H, int W,

@@ -74,6 +74,24 @@ def test_planners_reject_byte_ranges_past_32_bits():
     assert _native.call("ebsdvae_conv3x3_wgrad_split_slices", 1, 2048, 2048, 128, 128, PIECES_F16) < 0
 
 
+def test_queries_answer_as_the_entry_points_guard():
+    """Shapes an entry point refuses get no slice count / support from its query: the fp32
+    weight gradient tiles W = 8 as two whole 8 x 8 images (taller maps are refused; the cin = 1
+    and cout = 1 kernels take any tile), and the 64-pixel split-conv configurations are compiled
+    for one staged item per thread, which a 1 x 64 map exceeds."""
+    _ensure_built()
+    from latice import _native
+    from latice.engine import PIECES_F16
+    assert _native.call("ebsdvae_conv3x3_wgrad_slices", 3, 32, 8, 32, 32) == -1
+    assert _native.call("ebsdvae_conv3x3_wgrad_slices", 3, 16, 8, 128, 64) == -1
+    assert _native.call("ebsdvae_conv3x3_wgrad_slices", 3, 8, 8, 128, 128) > 0
+    assert _native.call("ebsdvae_conv3x3_wgrad_slices", 3, 32, 8, 1, 32) > 0
+    assert _native.call("ebsdvae_conv3x3_wgrad_slices", 3, 32, 8, 32, 1) > 0
+    for np_ in (3, PIECES_F16):
+        assert _native.call("ebsdvae_conv3x3_split_supported", 8, 8, 128, 128, np_) == 1
+        assert _native.call("ebsdvae_conv3x3_split_supported", 1, 64, 128, 128, np_) == 0
+
+
 def test_invalid_shapes_report_errors_without_gpu():
     _ensure_built()
     from latice import _native

@@ -943,25 +943,33 @@ def test_network_end_matches_oracle(cuda, monkeypatch, H, mfma):
     the float64 oracle; then the apply pass it feeds gives the block's output gradient.  Both
     forms: the split-fp16 MFMA kernel (default, round 6) and the fp32 VALU kernel (round 5)."""
     monkeypatch.setattr(E, "_NET_END_MFMA", mfma)
+    check_network_end(H, H)
+
+
+def check_network_end(H, W, ops=E, with_b14=True, with_g_loss=True):
+    """The body of test_network_end_matches_oracle on an (H, W) map.  ops supplies network_end
+    and in_backward_final_from (the engine's, or a caller's own with the engine's signatures:
+    tests/test_gpu_rect.py calls the C ABI on guarded buffers); without b14 / g_loss the entry
+    point gets NULL (bias 0, loss gradient 1)."""
     rng = np.random.default_rng(33)
     B, C = 3, 32
-    y = rng.standard_normal((B, H, H, C)) * 1.3 - 0.4
+    y = rng.standard_normal((B, H, W, C)) * 1.3 - 0.4
     xh, mean, rstd = O.instance_norm(y)
     st = np.stack([mean[:, 0, 0, :], rstd[:, 0, 0, :]], -1)
     w14 = rng.standard_normal((1, C, 3, 3)) * 0.15
-    b14 = np.array([0.07])
-    x = np.floor(rng.random((B, 1, H, H)) * 255) / 255
+    b14 = np.array([0.07 if with_b14 else 0.0])
+    x = np.floor(rng.random((B, 1, H, W)) * 255) / 255
     scale = 0.5
-    P = H * H
-    T = N.call("ebsdvae_net_end_tiles", H, H)
-    assert T == H // 64   # 64-row bands where H allows
+    P = H * W
+    T = N.call("ebsdvae_net_end_tiles", H, W)
+    assert T == H // (64 if H % 64 == 0 else 32)   # 64-row bands where H allows
     plan = E.build_plan()
-    params = {"decoder.14.weight": dev(w14), "decoder.14.bias": dev(b14)}
+    params = {"decoder.14.weight": dev(w14), "decoder.14.bias": dev(b14) if with_b14 else None}
     saved = {plan.dec[-1].name: (dev(y), dev(st))}
-    g_loss = torch.ones((), device="cuda")
-    x_hat, end = E.network_end(plan, saved, params, dev(x), g_loss=g_loss, scale=scale)
+    g_loss = torch.ones((), device="cuda") if with_g_loss else None
+    x_hat, end = ops.network_end(plan, saved, params, dev(x), g_loss=g_loss, scale=scale)
     a = O.lrelu(xh)
-    ref_xhat = O.conv3x3(a, w14, b14)[..., 0]                     # (B, H, H)
+    ref_xhat = O.conv3x3(a, w14, b14)[..., 0]                     # (B, H, W)
     sig = 1.0 / (1.0 + np.exp(-ref_xhat))
     ref_g1 = scale / (B * P) * (sig - x[:, 0])
     bce = (1 - x[:, 0]) * ref_xhat + np.maximum(-ref_xhat, 0) + np.log1p(np.exp(-np.abs(ref_xhat)))
@@ -978,7 +986,7 @@ def test_network_end_matches_oracle(cuda, monkeypatch, H, mfma):
     assert O.rel_err(part[..., 0], s1) < 1e-4 and O.rel_err(part[..., 1], s2) < 1e-4
     dw = torch.empty(1, C, 3, 3, device="cuda")
     db = torch.empty(1, device="cuda")
-    gy = E.in_backward_final_from(end, dev(w14), dev(y), dev(st), dw, db)
+    gy = ops.in_backward_final_from(end, dev(w14), dev(y), dev(st), dw, db)
     ref_gy = O.instance_norm_bwd(gxs, xh, rstd)
     rw, rb = O.conv3x3_wgrad(a, ref_g1[..., None])
     print(f"\nnet_end: gy {O.rel_err(host(gy), ref_gy):.2e} dW14 {O.rel_err(host(dw), rw):.2e} "
