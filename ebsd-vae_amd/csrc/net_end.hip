@@ -396,9 +396,10 @@ __global__ __launch_bounds__(ne_nth<W>(), W == 128 ? 2 : 1) void net_end_kernel(
 //       s1[c] = sum_q ga m      = sum_t w[c][t] (slope S[t] + (1 - slope) P[c][t]),
 //   m = lrelu'(xhat) in {1, slope} and S[t] = sum_q g1[q - d_t] (channel-free, on the VALU).
 // Every quantity is restricted to the band's own rows q, as in net_end_kernel, so the band
-// partials sum to the image's.  g1 is scaled by 2^kg (|g1| <= |cr| = the loss gradient scale,
-// known at launch) and the weights by 2^kw (their block-wide maximum) into fp16's range; both
-// are undone exactly.
+// partials sum to the image's.  g1 is scaled by 2^kg (|g1| <= |cr| max(1, |x|, |1 - x|), cr the
+// loss gradient scale and the maximum over the targets x of the rows whose g1 the band forms:
+// |cr| alone for targets in [0, 1]) and the weights by 2^kw (their block-wide maximum) into
+// fp16's range; both are undone exactly.
 template <int W> constexpr int nm_urs() { return W + 12; }  // plane row: col c at c + 4 (bank spread)
 template <int W> constexpr int nm_grs() { return W + 8; }   // g1 copy row (fp16): x at x + 4
 template <int W> constexpr size_t nm_lds() {
@@ -486,8 +487,6 @@ __global__ __launch_bounds__(2 * W, W == 128 ? 2 : 1) void net_end_mfma_kernel(
   const float uscale = ldexpf(1.f, -kw_);
   const float bias = b14 ? b14[0] : 0.f;
   const float cr = gscale * (g_loss ? *g_loss : 1.f);   // g_loss * scale / (B * P)
-  const int kg = f16_shift_of(fabsf(cr));               // |g1| <= |cr|
-  const float gsc = ldexpf(1.f, kg);
 
   // zero columns of the tap planes (col -1 and W), the two never-written g1 copy entries, and
   // the image (row r0 - 3 has no own-row (2); a defined image keeps the first pass finite)
@@ -556,7 +555,37 @@ __global__ __launch_bounds__(2 * W, W == 128 ? 2 : 1) void net_end_mfma_kernel(
   const int px0 = 4 * gq + qr, px1 = px0 + 16;
   // S[t]: column w feeds tap column kw = 0 unless w == 0, kw = 2 unless w == W - 1
   const float ml = (px_w + lane) != 0 ? 1.f : 0.f, mr = (px_w + lane) != W - 1 ? 1.f : 0.f;
+  // |sigmoid - x| <= max(|x|, |1 - x|): the largest over the target rows whose g1 this band
+  // forms (its own and the halo rows r0 - 1 and r0 + TH, inside the image) bounds |g1| / |cr|.
+  // (TH + 2) W / 4 four-pixel loads over the block, issued together behind the first y13 rows
+  // (x need not be 16-byte aligned); per wave here, across the waves after the barrier.
+  __shared__ float tmax_w[NWAVE];
+  {
+    typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
+    constexpr int NIT = ((TH + 2) * W / 4 + NTH - 1) / NTH;
+    const int lo = max(r0 - 1, 0), hi = min(r0 + TH + 1, H);
+    const float* xr = xt + (size_t)b * HW + (size_t)lo * W;
+    const int n4 = (hi - lo) * (W / 4);
+    f32x4u tv[NIT];
+#pragma unroll
+    for (int k = 0; k < NIT; ++k)   // past the end: the last four again (a maximum does not mind)
+      tv[k] = *reinterpret_cast<const f32x4u*>(xr + 4 * min(tid + k * NTH, n4 - 1));
+    float m = 0.f;
+#pragma unroll
+    for (int k = 0; k < NIT; ++k)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) m = fmaxf(m, fmaxf(fabsf(tv[k][e]), fabsf(1.f - tv[k][e])));
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+    if (lane == 0) tmax_w[wave] = m;
+  }
   __syncthreads();
+  // targets in [0, 1] give tm = 1: kg = f16_shift_of(|cr|), whatever the batch holds
+  float tm = 1.f;
+#pragma unroll
+  for (int wv = 0; wv < NWAVE; ++wv) tm = fmaxf(tm, tmax_w[wv]);
+  const int kg = f16_shift_of(fabsf(cr) * tm);   // |g1| <= |cr| tm
+  const float gsc = ldexpf(1.f, kg);
 
   auto step = [&](int i, float4 (&ycur)[2][2], float& tcur, f16x8 (&pn)[3][2], const f16x8 (&pb)[3][2])
                   EV_LAMBDA_INLINE {

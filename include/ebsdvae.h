@@ -484,6 +484,13 @@ int ebsdvae_vae_loss_fwd_parts(const float* bce_part, int tiles, const float* z,
  * once each.  The three contractions run on the split-fp16 MFMA (f16x3 products); the reduce
  * sums come from the weight-gradient contraction and an indicator contraction
  * (s2 = sum_t w G, s1 = sum_t w (slope S + (1 - slope) P), net_end.hip).
+ * Targets: x may hold any finite values (BCE-with-logits takes any target), at any float
+ * alignment.  g1 enters the two backward contractions as two fp16 pieces scaled by a power of
+ * two that each row band takes from its own targets, max(1, |x|, |1 - x|) over the rows whose
+ * g1 it forms: for x in [0, 1] the scale is that of g_loss * scale / (B * H * W) alone, and
+ * every output has the bits it has for any other batch in [0, 1]; one outlying target lowers
+ * the resolution of its band's part / wpart (about 2^-22 of the band's largest |g1|), not of
+ * x_hat, g1, bce_part or bpart.  NaN or infinite targets are outside the contract.
  * ebsdvae_net_end_valu: the same outputs from the fp32 VALU form (round 5; A/B). */
 int ebsdvae_net_end_tiles(int H, int W);
 int ebsdvae_net_end(const float* y13, const float* st13, const float* w14, const float* b14,

@@ -59,10 +59,16 @@ def fixture(name):
     return f, sd
 
 
+def oracle_fp64(name, x=None):
+    """The float64 forward of a fixture; x (float32, the fixture's shape) replaces its input."""
+    return _oracle_fp64(name, None if x is None else np.ascontiguousarray(x, np.float32).tobytes())
+
+
 @functools.lru_cache(maxsize=4)
-def oracle_fp64(name):
+def _oracle_fp64(name, x_bytes):
     f, sd = fixture(name)
-    outs, cache = O.forward(sd, f["x"], f["eps"])
+    x = f["x"] if x_bytes is None else np.frombuffer(x_bytes, np.float32).reshape(f["x"].shape)
+    outs, cache = O.forward(sd, x, f["eps"])
     return outs, cache
 
 
@@ -78,20 +84,22 @@ def blocks(plan, rec):
     return [one(L) for L in plan.enc], [one(L) for L in plan.dec]
 
 
-def check_grads(name, plan, rec, grads, label="", prec=None):
+def check_grads(name, plan, rec, grads, label="", prec=None, x=None):
     """grads: {state_dict name: GPU gradient tensor}; prec: the conv arithmetic that computed
-    them (default: the one in effect now).  Prints every error, then asserts."""
+    them (default: the one in effect now); x: the input and loss target the run used instead of
+    the fixture's.  Prints every error, then asserts."""
     from latice import engine as E
     prec = prec or E.get_precision()
     kz = ZERO_BIAS_K[prec]
     f, sd = fixture(name)
     kl = float(f["kl_lambda"])
+    xin = f["x"] if x is None else np.ascontiguousarray(x, np.float32)
     enc_b, dec_b = blocks(plan, rec)
-    _, cache_s, pins = O.forward_from_state(sd, f["x"], f["eps"], enc_b, dec_b)
-    g_state = O.backward(cache_s, f["x"], kl, pins=pins)
-    _, cache64 = oracle_fp64(name)
+    _, cache_s, pins = O.forward_from_state(sd, xin, f["eps"], enc_b, dec_b)
+    g_state = O.backward(cache_s, xin, kl, pins=pins)
+    _, cache64 = oracle_fp64(name, x)
     absum = {}
-    g_dec = O.backward(cache64, f["x"], kl, pins=pins, absum=absum)
+    g_dec = O.backward(cache64, xin, kl, pins=pins, absum=absum)
     rows, fails = [], []
     for n in g_state:
         g = host(grads[n])

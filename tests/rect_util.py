@@ -1,4 +1,5 @@
-"""Helpers of tests/test_gpu_rect.py: the C ABI called directly on rectangular (H != W) maps.
+"""Helpers of tests/test_gpu_rect.py (and, for the network end, tests/test_gpu_net_end_range.py):
+the C ABI called directly on rectangular (H != W) maps.
 
 Every output is carved out of a larger tensor filled with a sentinel (Guarded), with at least
 one image's worth of elements of slack before and after it, so an overrun of a row or an image
@@ -162,3 +163,49 @@ def finalize_bwd(part, B, C, T, HW):
 def band_max(gy, B, T):
     """max |gy| per row band of T bands per image (NHWC: a band is contiguous)."""
     return gy.abs().reshape(B, T, -1).amax(2)
+
+
+# ------------------------------------------------------------------------------ network end
+class AbiNetEnd:
+    """engine.network_end / in_backward_final_from on guarded buffers through the ABI; with
+    x_shift the targets sit that many floats past a 16-byte boundary."""
+
+    def __init__(self, mfma, x_shift=0):
+        self.name = "ebsdvae_net_end" if mfma else "ebsdvae_net_end_valu"
+        self.x_shift = x_shift
+
+    def network_end(self, plan, saved, params, x, g_loss=None, scale=1.0):
+        y13, st13 = saved[plan.dec[-1].name]
+        Bn, H, W, C = y13.shape
+        if self.x_shift:
+            buf = torch.empty(x.numel() + 4, device=x.device)
+            x = buf[self.x_shift:self.x_shift + x.numel()].view(x.shape).copy_(x)
+            assert x.data_ptr() % 16 == 4 * self.x_shift
+        T = N.call("ebsdvae_net_end_tiles", H, W)
+        assert T > 0
+        x_hat, g1, bce = Guarded((Bn, 1, H, W), Bn), Guarded((Bn, H, W), Bn), Guarded((Bn, T), Bn)
+        part = Guarded((Bn, T, C, 2), Bn, torch.float64)
+        wpart, bpart = Guarded((Bn * T, 9, 1, C), Bn), Guarded((Bn * T,), Bn)
+        outs = [x_hat, g1, bce, part, wpart, bpart]
+        assert run(self.name, outs, p(y13), p(st13), p(params["decoder.14.weight"]),
+                   p(params["decoder.14.bias"]), p(x), p(g_loss), float(scale), x_hat.ptr(), g1.ptr(),
+                   bce.ptr(), part.ptr(), wpart.ptr(), bpart.ptr(), Bn, H, W, C, stream(), must=True)
+        assert all(g.written() for g in outs)
+        return x_hat.t, E.NetEnd(g1.t, part.t, wpart.t, bpart.t, bce.t, T)
+
+    def in_backward_final_from(self, end, w14, y, st, dw14, db14):
+        Bn, H, W, C = y.shape
+        bst = finalize_bwd(end.part, Bn, C, end.tiles, H * W)
+        Tg = N.call("ebsdvae_in_bwd_final_tiles", H, W)
+        gy, gmax = Guarded(y.shape, Bn), Guarded((Bn, Tg), Bn)
+        assert run("ebsdvae_in_bwd_final_apply_max", [gy, gmax], p(end.g1), p(w14), p(y), p(st), p(bst),
+                   gy.ptr(), gmax.ptr(), Bn, H, W, C, stream(), must=True)
+        assert torch.equal(gmax.t, band_max(gy.t, Bn, Tg))
+        gy2 = Guarded(y.shape, Bn)   # the form without the maxima: the same gradient
+        assert run("ebsdvae_in_bwd_final_apply", [gy2], p(end.g1), p(w14), p(y), p(st), p(bst), gy2.ptr(),
+                   Bn, H, W, C, stream(), must=True)
+        assert torch.equal(gy.t, gy2.t)
+        dw, db = reduce_slices(end.wpart, end.bpart, Bn * end.tiles, C, 1, E.KIND_CONV)
+        dw14.copy_(dw)
+        db14.copy_(db)
+        return gy.t

@@ -337,6 +337,55 @@ def test_vae_loss_forward_backward(cuda, B, P):
     assert O.rel_err(host(g_std), c * ((z - mu) ** 2 / std ** 3 - 1 / std)) < 1e-5
 
 
+# (1, 252, 16): a single pattern; (300, 64, 64): the batch means stride past 256 patterns;
+# (2, 250, 256): the largest latent the entry points take, the scalar loop of P % 4 != 0
+@pytest.mark.parametrize("std_kind", ["lognormal", "1e-3"])
+@pytest.mark.parametrize("targets", ["unit", "u8"])
+@pytest.mark.parametrize("logit_std", [3, 200])
+@pytest.mark.parametrize("B,P,L", [(1, 252, 16), (300, 64, 64), (2, 250, 256)])
+def test_vae_loss_edges(cuda, B, P, L, logit_std, targets, std_kind):
+    """ebsdvae_vae_loss_fwd / _bwd at the edges of their shapes and input ranges, at the gates of
+    test_vae_loss_forward_backward: saturated logits (exp(-|x|) underflows, sigmoid is exactly 0
+    or 1), targets 0...255, a posterior of std 1e-3 (z - mu is 1e-3 of z).  The inputs are
+    rounded to float32 before the reference sees them: z - mu cancels, and the kernel is not to
+    be charged with the rounding of its own input.
+    The draw: with targets 0...255 a pattern's BCE sum runs over terms (1 - x) xhat of either
+    sign whose mean is zero, and what the 1e-6 gate then measures is how far one draw's terms
+    cancel: sum |term| / |sum term| is 50 ... 300 whatever the seed, and a float32 restatement
+    of the 256-thread strided sums, on the CPU, lands between 2e-7 and 3e-6 over 40 seeds at
+    B = 1.  With these seeds the restatement gives <= 1.7e-7 on loss and elbo and <= 1.2e-7 on
+    kl_loss over all 24 cases; the kernels (fixed summation order) <= 5.5e-7, the largest at
+    (1, 252, 16), logit std 3, targets 0...255, and <= 1.4e-7 wherever the targets are unit."""
+    rng = np.random.default_rng(35 + 1000 * B + P + L + logit_std)
+    f32 = lambda a: a.astype(np.float32).astype(np.float64)   # noqa: E731
+    xh = f32(rng.standard_normal((B, P)) * logit_std)
+    u = rng.random((B, P))
+    x = np.floor(u * 256) if targets == "u8" else np.floor(u * 255) / 255
+    x = f32(x)
+    mu = f32(rng.standard_normal((B, L)))
+    std = f32(np.exp(rng.standard_normal((B, L)) * 0.3) if std_kind == "lognormal" else np.full((B, L), 1e-3))
+    z = f32(mu + rng.standard_normal((B, L)) * std)
+    lam = 0.1
+    t = [dev(a) for a in (xh, x, z, mu, std)]
+    (loss, kl_loss, rec_loss), (elbo, kl, rec) = E.loss_forward(*t, lam)
+    ref = O.vae_loss(xh.reshape(B, 1, 1, P), x.reshape(B, 1, 1, P), z, mu, std, lam)
+    print(f"\nvae_loss B {B} P {P} L {L}: loss {abs(float(loss) - ref['loss']) / max(1, abs(ref['loss'])):.2e} "
+          f"kl {abs(float(kl_loss) - ref['kl_loss']) / max(1e-3, abs(ref['kl_loss'])):.2e} "
+          f"elbo {O.rel_err(host(elbo), ref['elbo']):.2e}")
+    assert abs(float(loss) - ref["loss"]) < 1e-6 * max(1, abs(ref["loss"]))
+    assert abs(float(kl_loss) - ref["kl_loss"]) < 1e-5 * max(1e-3, abs(ref["kl_loss"]))
+    assert O.rel_err(host(elbo), ref["elbo"]) < 1e-6
+    one = torch.ones((), device="cuda")
+    g_xhat, g_z, g_mu, g_std, g_x = E.loss_backward(*t, lam, g_loss=one, need_gx=True)
+    sig = np.exp(-np.logaddexp(0.0, -xh))   # overflow-safe, as O.vae_loss
+    assert O.rel_err(host(g_xhat), (sig - x) / (P * B)) < 1e-5
+    assert O.rel_err(host(g_x), -xh / (P * B)) < 1e-5
+    c = lam / (B * L)
+    assert O.rel_err(host(g_z), c * (z - (z - mu) / std ** 2)) < 1e-5
+    assert O.rel_err(host(g_mu), c * (z - mu) / std ** 2) < 1e-5
+    assert O.rel_err(host(g_std), c * ((z - mu) ** 2 / std ** 3 - 1 / std)) < 1e-5
+
+
 def test_normal_sampler(cuda):
     a = torch.empty(1 << 20, device="cuda")
     b = torch.empty(1 << 20, device="cuda")
@@ -946,19 +995,50 @@ def test_network_end_matches_oracle(cuda, monkeypatch, H, mfma):
     check_network_end(H, H)
 
 
-def check_network_end(H, W, ops=E, with_b14=True, with_g_loss=True):
+def net_end_targets(u, kind, H):
+    """BCE targets (B, 1, H, W) from uniform draws u in [0, 1), for check_network_end:
+      unit  floor(u 255) / 255, the 8-bit patterns every other test feeds;
+      u8    floor(u 256), an unnormalised batch 0...255;
+      neg   uniform in [-3, 4);
+      hot   unit, with 255 at columns 0 and W - 1 of rows 0, e - 1, e and H - 1, e the first
+            band edge (the first row of the second band; on a one-band map H - 1)."""
+    if kind == "u8":
+        return np.floor(u * 256)
+    if kind == "neg":
+        return u * 7 - 3
+    x = np.floor(u * 255) / 255
+    if kind == "hot":
+        T = H // (64 if H % 64 == 0 else 32)
+        e = H // T if T > 1 else H - 1
+        for r in (0, e - 1, e, H - 1):
+            x[:, 0, r, 0] = x[:, 0, r, -1] = 255.0
+    else:
+        assert kind == "unit", kind
+    return x
+
+
+def check_network_end(H, W, ops=E, with_b14=True, with_g_loss=True, *, targets="unit", wscale=1.0,
+                      g_loss_value=1.0, planes=False, B=3):
     """The body of test_network_end_matches_oracle on an (H, W) map.  ops supplies network_end
     and in_backward_final_from (the engine's, or a caller's own with the engine's signatures:
     tests/test_gpu_rect.py calls the C ABI on guarded buffers); without b14 / g_loss the entry
-    point gets NULL (bias 0, loss gradient 1)."""
+    point gets NULL (bias 0, loss gradient 1).  The keyword arguments shape the inputs
+    (tests/test_gpu_net_end_range.py; the defaults are the draws of the tests above): targets as
+    net_end_targets, w14 times wscale, the loss gradient g_loss_value, and with planes two
+    degenerate planes in image 0 of y13: channel 5 one pixel 1 among zeros (xhat ~ 90 there, the
+    rest on the slope branch at -1e-2), channel 7 constant (variance 0, xhat = 0 everywhere)."""
     rng = np.random.default_rng(33)
-    B, C = 3, 32
+    C = 32
     y = rng.standard_normal((B, H, W, C)) * 1.3 - 0.4
+    if planes:
+        y[0, :, :, 5] = 0.0
+        y[0, H // 2, W - 1, 5] = 1.0
+        y[0, :, :, 7] = 0.25
     xh, mean, rstd = O.instance_norm(y)
     st = np.stack([mean[:, 0, 0, :], rstd[:, 0, 0, :]], -1)
-    w14 = rng.standard_normal((1, C, 3, 3)) * 0.15
+    w14 = rng.standard_normal((1, C, 3, 3)) * 0.15 * wscale
     b14 = np.array([0.07 if with_b14 else 0.0])
-    x = np.floor(rng.random((B, 1, H, W)) * 255) / 255
+    x = net_end_targets(rng.random((B, 1, H, W)), targets, H)
     scale = 0.5
     P = H * W
     T = N.call("ebsdvae_net_end_tiles", H, W)
@@ -966,34 +1046,48 @@ def check_network_end(H, W, ops=E, with_b14=True, with_g_loss=True):
     plan = E.build_plan()
     params = {"decoder.14.weight": dev(w14), "decoder.14.bias": dev(b14) if with_b14 else None}
     saved = {plan.dec[-1].name: (dev(y), dev(st))}
-    g_loss = torch.ones((), device="cuda") if with_g_loss else None
+    g_loss = torch.full((), g_loss_value, device="cuda") if with_g_loss else None
+    gl = float(np.float32(g_loss_value)) if with_g_loss else 1.0
     x_hat, end = ops.network_end(plan, saved, params, dev(x), g_loss=g_loss, scale=scale)
     a = O.lrelu(xh)
+    if planes:   # the constant plane is exactly 0 after the norm, on the slope branch
+        assert (xh[0, :, :, 7] == 0).all() and xh[0, H // 2, W - 1, 5] > 80
     ref_xhat = O.conv3x3(a, w14, b14)[..., 0]                     # (B, H, W)
-    sig = 1.0 / (1.0 + np.exp(-ref_xhat))
-    ref_g1 = scale / (B * P) * (sig - x[:, 0])
-    bce = (1 - x[:, 0]) * ref_xhat + np.maximum(-ref_xhat, 0) + np.log1p(np.exp(-np.abs(ref_xhat)))
-    assert O.rel_err(host(x_hat)[:, 0], ref_xhat) < 2e-5
-    assert O.rel_err(host(end.g1), ref_g1) < 2e-5
+    # sigmoid and BCE in the overflow-safe form of O.vae_loss
+    sig = np.exp(-np.logaddexp(0.0, -ref_xhat))
+    ref_g1 = gl * scale / (B * P) * (sig - x[:, 0])
+    bce = (1 - x[:, 0]) * ref_xhat + np.logaddexp(0.0, -ref_xhat)
+    got = {"x_hat": host(x_hat), "g1": host(end.g1), "bce": host(end.bce), "part": host(end.part),
+           "wpart": host(end.wpart), "bpart": host(end.bpart)}
+    bad = [k for k, v in got.items() if not np.isfinite(v).all()]
+    assert not bad, f"non-finite outputs: {bad}"
+    assert O.rel_err(got["x_hat"][:, 0], ref_xhat) < 2e-5
+    assert O.rel_err(got["g1"], ref_g1) < 2e-5
     ref_bce = bce.reshape(B, T, -1).sum(-1)
-    assert O.rel_err(host(end.bce), ref_bce) < 1e-5
+    assert O.rel_err(got["bce"], ref_bce) < 1e-5
     # reduce sums of the last block, finalized, and the apply that consumes them
     ga = O.conv3x3_dgrad(ref_g1[..., None], w14)
     gxs = ga * O.lrelu_slope(xh)
     s1 = gxs.reshape(B, T, -1, C).sum(2)
     s2 = (gxs * xh).reshape(B, T, -1, C).sum(2)
-    part = host(end.part)
+    part = got["part"]
+    print(f"\nnet_end {H}x{W}: s1 {O.rel_err(part[..., 0], s1):.2e} s2 {O.rel_err(part[..., 1], s2):.2e}")
     assert O.rel_err(part[..., 0], s1) < 1e-4 and O.rel_err(part[..., 1], s2) < 1e-4
     dw = torch.empty(1, C, 3, 3, device="cuda")
     db = torch.empty(1, device="cuda")
     gy = ops.in_backward_final_from(end, dev(w14), dev(y), dev(st), dw, db)
     ref_gy = O.instance_norm_bwd(gxs, xh, rstd)
     rw, rb = O.conv3x3_wgrad(a, ref_g1[..., None])
-    print(f"\nnet_end: gy {O.rel_err(host(gy), ref_gy):.2e} dW14 {O.rel_err(host(dw), rw):.2e} "
+    print(f"net_end: gy {O.rel_err(host(gy), ref_gy):.2e} dW14 {O.rel_err(host(dw), rw):.2e} "
           f"db14 {O.rel_err(host(db), rb):.2e}")
+    assert np.isfinite(host(gy)).all() and np.isfinite(host(dw)).all() and np.isfinite(host(db)).all()
     assert O.rel_err(host(gy), ref_gy) < 1e-4
     assert O.rel_err(host(dw), rw) < 5e-5
     assert O.rel_err(host(db), rb) < 5e-5
+    if gl == 0:   # rel_err has a floor: a zero loss gradient gives exact zeros
+        for k in ("g1", "part", "wpart", "bpart"):
+            assert (got[k] == 0).all(), k
+        assert (host(gy) == 0).all() and (host(dw) == 0).all() and (host(db) == 0).all()
     # the loss values from the band sums
     z = rng.standard_normal((B, 16)); mu = rng.standard_normal((B, 16)) * 0.3
     sd = np.exp(rng.standard_normal((B, 16)) * 0.2)
@@ -1001,4 +1095,3 @@ def check_network_end(H, W, ops=E, with_b14=True, with_g_loss=True):
     ref = O.vae_loss(ref_xhat[:, None], x, z, mu, sd, 5e-6)
     assert abs(float(loss) - ref["loss"]) <= 1e-5 * abs(ref["loss"])
     assert O.rel_err(host(elbo), ref["elbo"]) < 1e-5
-

@@ -24,7 +24,7 @@ from latice import _native as N
 from latice import engine as E
 from latice.data_module import PatternCorrection, correct_patterns
 from oracle import vae_oracle as O
-from rect_util import Guarded, dev, host, p, run
+from rect_util import AbiNetEnd, Guarded, dev, host, p, run
 from test_gpu_pattern_correction import GATE, THREE_PAIRS, _correction
 
 pytestmark = pytest.mark.gpu
@@ -49,45 +49,6 @@ def _frozen(*arrays):
 
 
 # ============================================================== 7. network ends
-class AbiNetEnd:
-    """engine.network_end / in_backward_final_from on guarded buffers through the ABI."""
-
-    def __init__(self, mfma):
-        self.name = "ebsdvae_net_end" if mfma else "ebsdvae_net_end_valu"
-
-    def network_end(self, plan, saved, params, x, g_loss=None, scale=1.0):
-        y13, st13 = saved[plan.dec[-1].name]
-        Bn, H, W, C = y13.shape
-        T = N.call("ebsdvae_net_end_tiles", H, W)
-        assert T > 0
-        x_hat, g1, bce = Guarded((Bn, 1, H, W), Bn), Guarded((Bn, H, W), Bn), Guarded((Bn, T), Bn)
-        part = Guarded((Bn, T, C, 2), Bn, torch.float64)
-        wpart, bpart = Guarded((Bn * T, 9, 1, C), Bn), Guarded((Bn * T,), Bn)
-        outs = [x_hat, g1, bce, part, wpart, bpart]
-        assert run(self.name, outs, p(y13), p(st13), p(params["decoder.14.weight"]),
-                   p(params["decoder.14.bias"]), p(x), p(g_loss), float(scale), x_hat.ptr(), g1.ptr(),
-                   bce.ptr(), part.ptr(), wpart.ptr(), bpart.ptr(), Bn, H, W, C, U.stream(), must=True)
-        assert all(g.written() for g in outs)
-        return x_hat.t, E.NetEnd(g1.t, part.t, wpart.t, bpart.t, bce.t, T)
-
-    def in_backward_final_from(self, end, w14, y, st, dw14, db14):
-        Bn, H, W, C = y.shape
-        bst = U.finalize_bwd(end.part, Bn, C, end.tiles, H * W)
-        Tg = N.call("ebsdvae_in_bwd_final_tiles", H, W)
-        gy, gmax = Guarded(y.shape, Bn), Guarded((Bn, Tg), Bn)
-        assert run("ebsdvae_in_bwd_final_apply_max", [gy, gmax], p(end.g1), p(w14), p(y), p(st), p(bst),
-                   gy.ptr(), gmax.ptr(), Bn, H, W, C, U.stream(), must=True)
-        assert torch.equal(gmax.t, U.band_max(gy.t, Bn, Tg))
-        gy2 = Guarded(y.shape, Bn)   # the form without the maxima: the same gradient
-        assert run("ebsdvae_in_bwd_final_apply", [gy2], p(end.g1), p(w14), p(y), p(st), p(bst), gy2.ptr(),
-                   Bn, H, W, C, U.stream(), must=True)
-        assert torch.equal(gy.t, gy2.t)
-        dw, db = U.reduce_slices(end.wpart, end.bpart, Bn * end.tiles, C, 1, E.KIND_CONV)
-        dw14.copy_(dw)
-        db14.copy_(db)
-        return gy.t
-
-
 # (32,128), (96,128), (32,256): 32-row bands (1, 3, 1 per image); (64,128): one 64-row band
 @pytest.mark.parametrize("mfma", [True, False], ids=["mfma", "valu"])
 @pytest.mark.parametrize("H,W", [(32, 128), (96, 128), (64, 128), (32, 256)])

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 import torch
 
-from pinned import check_grads, fixture, host
+from pinned import check_grads, fixture, host, oracle_fp64
 from latice import engine as E
 from latice.model import VariationalAutoEncoderRawData
 from latice.trainer import VAETrainer
@@ -47,6 +47,33 @@ def test_trainer_forward_backward_vs_pinned_oracle(cuda, name, prec):
         ref = float(f[k])
         assert abs(float(v) - ref) <= 1e-5 * abs(ref) + 1e-12, k
     check_grads(name, m.plan, rec, tr.G, label=f"trainer {prec}", prec=prec)
+
+
+@pytest.mark.parametrize("prec", ["f16x3", "fp32"])
+def test_trainer_unnormalised_batch_vs_pinned_oracle(cuda, prec):
+    """An unnormalised batch: vae128_b4's patterns times 255 (0...255) as input and as BCE
+    target, which the reference's loss takes as it takes any target.  |sigmoid - x| reaches 255
+    in the logit gradient the fused network end splits into fp16 pieces; loss scalars and
+    every gradient at the gates of test_trainer_forward_backward_vs_pinned_oracle."""
+    name = "vae128_b4"
+    f, m = build(name, cuda)
+    x255 = (f["x"] * np.float32(255)).astype(np.float32)
+    assert x255.max() > 250
+    x = torch.from_numpy(x255).to(cuda)
+    eps = torch.from_numpy(f["eps"]).to(cuda)
+    kl_lambda = float(f["kl_lambda"])
+    with E.precision(prec):
+        tr = VAETrainer(m, kl_lambda=kl_lambda)
+        assert E.net_end_ok(m.plan)
+        with E.record_state() as rec:
+            loss, kl, rec_loss = tr.forward_backward(x, eps)
+        torch.cuda.synchronize()
+    outs, _ = oracle_fp64(name, x255)
+    ref = O.vae_loss(outs["x_hat"], x255, outs["z"], outs["mu"], outs["std"], kl_lambda)
+    for k, v in (("loss", loss), ("kl_loss", kl), ("recon_loss", rec_loss)):
+        assert abs(float(v) - ref[k]) <= 1e-5 * abs(ref[k]) + 1e-12, k
+    assert all(bool(torch.isfinite(g).all()) for g in tr.G.values())
+    check_grads(name, m.plan, rec, tr.G, label=f"trainer x255 {prec}", prec=prec, x=x255)
 
 
 def test_trainer_step_is_adam_on_the_checked_gradient(cuda):
