@@ -373,13 +373,6 @@ int heads_tile(int B, int SS, int n) {
   return bt;
 }
 
-template <typename K>
-void heads_lds_attr(K kernel, size_t lds) {
-  if (lds > 64 * 1024)
-    (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)lds);
-}
-
 // feature chunks of the partial pass: CC channels (a power of two dividing C) x all SS pixels,
 // about 128 features each; KS = C / CC chunks
 int heads_cc(int C, int SS) {
@@ -389,15 +382,47 @@ int heads_cc(int C, int SS) {
 }
 int heads_ks(int C, int SS) { return C / heads_cc(C, SS); }
 
+// One launch's tile: bt patterns per block, R per thread, dynamic LDS bytes.  The launchers
+// launch what these return and heads_shape_ok admits a shape only if every launch of the three
+// entry points is ok(), so the size query and the entry points answer alike.
+constexpr size_t HEADS_LDS_MAX = 160 * 1024;
+struct HeadsLaunch {
+  int bt, R;
+  size_t lds;
+  bool ok() const { return lds <= HEADS_LDS_MAX && (R == 1 || R == 2 || R == 4 || R == 8); }
+};
+
+// heads_dot_partial over N output rows: Wl [KC][NP + 1] + Al [bt][KC + 1]
+HeadsLaunch heads_partial_launch(int B, int C, int SS, int N) {
+  const int NP = heads_np(N);
+  const int CC = heads_cc(C, SS), KS = C / CC;
+  const size_t KC = (size_t)CC * SS;
+  const int bt = heads_tile(B, KS, NP);
+  return {bt, bt * NP / HT, (KC * (NP + 1) + (size_t)bt * (KC + 1)) * sizeof(float)};
+}
+
+// heads_expand over J latent columns: Ml [J][C] + Vl [bt][J]
+HeadsLaunch heads_expand_launch(int B, int C, int SS, int J) {
+  const int bt = heads_tile(B, SS, C);
+  return {bt, bt * C / HT, ((size_t)J * C + (size_t)bt * J) * sizeof(float)};
+}
+
+template <typename K>
+void heads_lds_attr(K kernel, size_t lds) {
+  if (lds > 64 * 1024)
+    (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)lds);
+}
+
 template <int MODE>
 int launch_partial(const float* A, const float* w0, const float* w1, float* part, float* copy,
                    int cstride, int coff, int B, int C, int SS, int L, int N, hipStream_t st) {
   const int NP = heads_np(N);
   const int CC = heads_cc(C, SS), KS = C / CC, KC = CC * SS;
-  const int bt = heads_tile(B, KS, NP);
-  const int R = bt * NP / HT;
-  const size_t lds = ((size_t)KC * (NP + 1) + (size_t)bt * (KC + 1)) * sizeof(float);
-  EV_REQUIRE(lds <= 160 * 1024, "heads: feature chunk of %d too large", KC);
+  const HeadsLaunch t = heads_partial_launch(B, C, SS, N);
+  const int bt = t.bt, R = t.R;
+  const size_t lds = t.lds;
+  EV_REQUIRE(lds <= HEADS_LDS_MAX, "heads: feature chunk of %d too large", KC);
   const dim3 grid(KS, (B + bt - 1) / bt);
 #define EV_HP(RR)                                                                              \
   case RR:                                                                                     \
@@ -416,10 +441,10 @@ int launch_partial(const float* A, const float* w0, const float* w1, float* part
 template <int MODE>
 int launch_expand(const float* V, int vstride, const float* m0, const float* m1, const float* bias,
                   float* out, int B, int C, int SS, int L, int J, hipStream_t st) {
-  const int bt = heads_tile(B, SS, C);
-  const int R = bt * C / HT;
-  const size_t lds = ((size_t)J * C + (size_t)bt * J) * sizeof(float);
-  EV_REQUIRE(lds <= 160 * 1024, "heads: expand tile too large");
+  const HeadsLaunch t = heads_expand_launch(B, C, SS, J);
+  const int bt = t.bt, R = t.R;
+  const size_t lds = t.lds;
+  EV_REQUIRE(lds <= HEADS_LDS_MAX, "heads: expand tile too large");
   const dim3 grid(SS, (B + bt - 1) / bt);
 #define EV_HE(RR)                                                                              \
   case RR:                                                                                     \
@@ -435,9 +460,17 @@ int launch_expand(const float* V, int vstride, const float* m0, const float* m1,
   return 0;
 }
 
+// The shapes the three entry points run: every launch they would make fits its tile and the
+// 160 KiB of LDS.  heads_fwd: partial MODE 0 over 2L rows, expand over L; latent_mu: partial
+// MODE 0 over L rows; heads_bwd: partial MODE 1 over L rows (the LDS of a partial launch does
+// not depend on MODE), expand over 2L.
 bool heads_shape_ok(int B, int C, int S, int L) {
-  return B > 0 && L > 0 && L <= MAXL && S > 0 && S <= 1024 && C >= 16 && C <= 256 &&
-         (C & (C - 1)) == 0;
+  if (!(B > 0 && L > 0 && L <= MAXL && S > 0 && S <= 1024 && C >= 16 && C <= 256 &&
+        (C & (C - 1)) == 0))
+    return false;
+  const int SS = S * S;
+  return heads_partial_launch(B, C, SS, 2 * L).ok() && heads_partial_launch(B, C, SS, L).ok() &&
+         heads_expand_launch(B, C, SS, L).ok() && heads_expand_launch(B, C, SS, 2 * L).ok();
 }
 
 }  // namespace

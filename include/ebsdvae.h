@@ -392,7 +392,16 @@ int ebsdvae_upsample2_bwd(const float* g, float* out, int B, int H, int W, int C
  * dec_in = Linear(L,F)(z) viewed (B,C,S,S) and written NHWC. */
 /* work: ebsdvae_heads_work(B,C,S,L) bytes of caller-owned device scratch (split-K partial
  * sums over the S*S feature pixels; shared by heads_fwd / latent_mu / heads_bwd on one
- * stream).  C: a power of two in 16..256; L <= 64. */
+ * stream).  C: a power of two in 16..256; 1 <= L <= 64; B >= 1.  S is bounded by the 160 KiB
+ * of LDS one block may hold: the partial pass stages a chunk of KC features (KC = S*S once
+ * S*S > 64, else the largest power-of-two multiple of S*S up to 128) as KC x (NP + 1) weights
+ * and bt x (KC + 1) inputs, NP = 2L rounded up to a power of two >= 16 and bt * NP >= 256
+ * (bt: 256 / NP ... 2048 / NP patterns per block, fewer while the grid stays under 256
+ * blocks, so it depends on B and C).  Every S <= 16 is admitted at every B, C and L; beyond
+ * that it depends on all four (S = 17 at L = 64 and S = 35 at L <= 8 run for a few patterns
+ * with few channels), and no S > 35 is admitted.  The expand pass (2L x C + bt x 2L floats)
+ * always fits.  Returns 0 for every (B,C,S,L) the three entry points refuse, and they refuse (nonzero,
+ * ebsdvae_last_error names the shape, nothing launched) exactly those. */
 size_t ebsdvae_heads_work(int B, int C, int S, int L);
 int ebsdvae_heads_fwd(const float* enc, const float* w_mu, const float* b_mu,
                       const float* w_lv, const float* b_lv, const float* w_l2,

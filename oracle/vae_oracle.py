@@ -304,8 +304,12 @@ def blocks_from_cache(cache):
     return blocks("enc"), blocks("dec")
 
 
-def backward(cache, x_nchw, kl_lambda, g_loss: float = 1.0, pins=None, absum=None):
+def backward(cache, x_nchw, kl_lambda, g_loss: float = 1.0, pins=None, absum=None, upstream=None):
     """Gradients of compute_loss(...)['loss'] w.r.t. every parameter (state_dict names).
+
+    upstream (optional): {"x_hat" (B,H,W,1), "z", "mu", "std"} -- the gradients of another
+    scalar w.r.t. the model's four outputs, taken instead of the loss's own (x_nchw, kl_lambda
+    and g_loss are then unused): the parameter gradients of that scalar.
 
     pins (optional): {("enc"|"dec", i): (pos, arg)} from pinned_routing -- the LeakyReLU
     branch and max-pool argmax of block i are taken from there instead of from this
@@ -322,6 +326,8 @@ def backward(cache, x_nchw, kl_lambda, g_loss: float = 1.0, pins=None, absum=Non
     npx = xh_last.shape[1] * xh_last.shape[2]
     sig = 1.0 / (1.0 + np.exp(-xh_last))
     g = g_loss * (sig - x) / (npx * bsz)                       # d loss / d x_hat (NHWC, C=1)
+    if upstream is not None:
+        g = np.asarray(upstream["x_hat"], np.float64).reshape(xh_last.shape)
     dw, db = conv3x3_wgrad(cache["last_in"], g)
     grads["decoder.14.weight"], grads["decoder.14.bias"] = dw, db
     ga = conv3x3_dgrad(g, p["decoder.14.weight"])
@@ -347,9 +353,13 @@ def backward(cache, x_nchw, kl_lambda, g_loss: float = 1.0, pins=None, absum=Non
     g_out = nchw_flatten(ga)                                    # grad wrt linear2 output
     grads["linear2.0.weight"] = g_out.T @ z
     grads["linear2.0.bias"] = g_out.sum(0)
-    gz = g_out @ p["linear2.0.weight"] + kscale * (z - (z - mu) / std ** 2)
-    gmu = gz + kscale * ((z - mu) / std ** 2)
+    dz = kscale * (z - (z - mu) / std ** 2)
+    dmu = kscale * ((z - mu) / std ** 2)
     gstd = kscale * ((z - mu) ** 2 / std ** 3 - 1.0 / std)
+    if upstream is not None:
+        dz, dmu, gstd = (np.asarray(upstream[k], np.float64) for k in ("z", "mu", "std"))
+    gz = g_out @ p["linear2.0.weight"] + dz
+    gmu = gz + dmu
     glv = (gstd + gz * e) * std / 2.0
     grads["mu.0.weight"], grads["mu.0.bias"] = gmu.T @ flat, gmu.sum(0)
     grads["logvar.0.weight"], grads["logvar.0.bias"] = glv.T @ flat, glv.sum(0)

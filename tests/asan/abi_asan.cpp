@@ -129,7 +129,11 @@ int main(int argc, char** argv) {
                                nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 2, 128,
                                4, 16, nullptr), "heads_fwd null");
   if (ebsdvae_heads_work(256, 128, 4, 16) != (size_t)16 * 256 * 32 * 4 ||
-      ebsdvae_heads_work(2, 96, 4, 16) != 0 || ebsdvae_heads_work(2, 128, 4, 65) != 0) {
+      ebsdvae_heads_work(2, 96, 4, 16) != 0 || ebsdvae_heads_work(2, 128, 4, 65) != 0 ||
+      // the staged chunk past 160 KiB of LDS: S = 17 is the last that runs at L = 64
+      ebsdvae_heads_work(4, 16, 17, 64) != (size_t)16 * 4 * 128 * 4 ||
+      ebsdvae_heads_work(4, 16, 18, 64) != 0 || ebsdvae_heads_work(4, 128, 40, 4) != 0 ||
+      ebsdvae_heads_work(1, 256, 1024, 64) != 0) {
     printf("FAIL heads_work\n");
     ++g_fail;
   }

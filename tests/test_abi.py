@@ -90,6 +90,22 @@ def test_queries_answer_as_the_entry_points_guard():
     for np_ in (3, PIECES_F16):
         assert _native.call("ebsdvae_conv3x3_split_supported", 8, 8, 128, 128, np_) == 1
         assert _native.call("ebsdvae_conv3x3_split_supported", 1, 64, 128, 128, np_) == 0
+    # the latent heads: a scratch size for the shapes the entry points run, 0 for those they
+    # refuse -- the staged chunk of the partial pass past 160 KiB of LDS among them
+    # (tests/test_gpu_heads_shapes.py makes the entry points' half of the comparison)
+    import heads_ref as H
+    for C, S, L, B in H.HEADS_CASES + H.PLAN_SHAPES + [H.LARGEST_ADMITTED]:
+        assert _native.call("ebsdvae_heads_work", B, C, S, L) > 0, (B, C, S, L)
+    for B, C, S, L in H.REFUSED:
+        assert _native.call("ebsdvae_heads_work", B, C, S, L) == 0, (B, C, S, L)
+    # and byte for byte what the host-side port of the launch planning says, around every
+    # boundary of the family
+    for B in (0, 1, 4, 9, 129, 300, 2000, 70000):
+        for C in (8, 16, 32, 48, 64, 128, 256, 512):
+            for S in (0, 1, 2, 3, 8, 11, 12, 16, 17, 18, 24, 25, 31, 32, 35, 36, 40, 1024, 1025):
+                for L in (0, 1, 7, 8, 9, 16, 17, 32, 33, 64, 65):
+                    assert _native.call("ebsdvae_heads_work", B, C, S, L) == \
+                        H.heads_work_bytes(B, C, S, L), (B, C, S, L)
 
 
 def test_invalid_shapes_report_errors_without_gpu():
