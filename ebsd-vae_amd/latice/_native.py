@@ -110,6 +110,7 @@ SIGNATURES = {
     "ebsdvae_correct_patterns": [P, I, I, I, I, I, I, P, I, P, I, I, P, P, P],
     "ebsdvae_correct_patterns_work": [I, I, I],
     "ebsdvae_accumulate_patterns": [P, I, I, I, I, P, P],
+    "ebsdvae_resample_patterns": [P, I, I, I, I, I, I, I, I, I, I, P, P, I, P, P, I, F, P, P],
     "ebsdvae_average_neighbours": [P, I64, I, I, I64, I64, P, I, I, I, I, P, P],
     "ebsdvae_index_latents_work": [I64, I, I, I],
     "ebsdvae_index_latents": [P, I64, P, P, I, I, I, ctypes.c_double, I, I, P, P, P, P, P, P, P, P, P],

@@ -25,7 +25,10 @@ Beyond the reference: raw detector patterns are background-corrected on the devi
 per-pattern rescale; csrc/correct.hip), the ingest `index_scan(correction=...)` uses, and
 transformed patterns are averaged with their neighbours on the scan grid by
 `average_neighbour_patterns(x, NeighbourAverage(...))` (csrc/neighbour.hip), the stage
-`index_scan(neighbour_average=...)` puts between ingest and encoder.
+`index_scan(neighbour_average=...)` puts between ingest and encoder.  Detector-size patterns
+are binned to the model's input size in front of either ingest by
+`resample_patterns(raw, image_size, DetectorResample(...))` (the exact area mean;
+csrc/resample.hip), the stage `index_scan(resample=...)` and `correct_patterns(resample=...)` use.
 
 Lightning is optional: DPDataModule subclasses `pl.LightningDataModule` when
 pytorch_lightning is importable.  There is no CPU fallback: the transform runs on the ROCm
@@ -216,16 +219,205 @@ class PatternCorrection:
         return st
 
 
+# ---------------------------------------------------------------- detector resampling
+MAX_RESAMPLED_SIDE = 256    # ebsdvae_resample_patterns' output limit per axis
+MAX_RESAMPLE_FACTOR = 8     # ... and its largest region / output ratio per axis
+
+
+def resample_axis(R: int, O: int) -> tuple[np.ndarray, np.ndarray]:
+    """The area-mean tables of one axis: a region of R source pixels onto O output pixels,
+    O <= R.  Source pixel x overlaps output pixel j by
+    max(0, min((j + 1) R, (x + 1) O) - max(j R, x O)) / O output pixels: an integer numerator,
+    the quotient taken in float64 and rounded to float32.  Returns (start (O,) int32, weights
+    (O, T) float32): output j sums weights[j, t] * source[start[j] + t] over its T taps,
+    T = the largest number of source pixels an output overlaps (at most ceil(R / O) + 1).  An
+    output that overlaps fewer has zero weights behind them, or in front where the window would
+    otherwise leave the region: every tap lies inside [0, R)."""
+    R, O = int(R), int(O)
+    if not 1 <= O <= R:
+        raise ValueError(f"resample_axis: {R} source pixels onto {O} (downsampling only)")
+    j = np.arange(O, dtype=np.int64)
+    first = j * R // O                         # floor(j R / O)
+    last = ((j + 1) * R + O - 1) // O          # ceil((j + 1) R / O), exclusive
+    T = int((last - first).max())
+    start = np.minimum(first, R - T)
+    x = start[:, None] + np.arange(T, dtype=np.int64)[None, :]
+    num = np.minimum((j[:, None] + 1) * R, (x + 1) * O) - np.maximum(j[:, None] * R, x * O)
+    weights = (np.maximum(num, 0).astype(np.float64) / float(O)).astype(np.float32)
+    return start.astype(np.int32), weights
+
+
+@dataclass(frozen=True, eq=False)
+class DetectorResample:
+    """Binning of raw detector patterns to the model's input size, applied by
+    `resample_patterns`, `correct_patterns(resample=...)` and `index_scan(resample=...)`: the
+    exact area mean (a box filter with fractional pixel overlap) of the region `roi` =
+    (top, left, height, width) of the (H0, W0) pattern on the (h, w) output grid, by a factor of
+    1 to 8 per axis, independently.  `roi=None` takes the centred largest window of the output's
+    aspect ratio: with g = gcd(h, w) and m = min(H0 // (h / g), W0 // (w / g)) the window
+    (m h / g, m w / g), at the centre-crop offsets; for a square model the centred square of
+    side min(H0, W0)."""
+
+    roi: tuple | None = None
+    # per (device, region size, output size): the uploaded tables (filled on first use)
+    _device_state: dict = field(default_factory=dict, init=False, repr=False)
+
+    def __post_init__(self):
+        if self.roi is not None:
+            try:
+                roi = tuple(int(v) for v in self.roi)
+            except (TypeError, ValueError):
+                raise ValueError(f"roi must be (top, left, height, width), got {self.roi!r}") from None
+            if len(roi) != 4:
+                raise ValueError(f"roi must be (top, left, height, width), got {self.roi!r}")
+            object.__setattr__(self, "roi", roi)
+
+    def window(self, H0: int, W0: int, h: int, w: int) -> tuple[int, int, int, int]:
+        """The region (top, left, height, width) of an (H0, W0) pattern that goes to (h, w)."""
+        if self.roi is not None:
+            return self.roi
+        H0, W0, h, w = int(H0), int(W0), int(h), int(w)
+        if min(H0, W0, h, w) < 1:
+            raise ValueError(f"pattern ({H0}, {W0}) / output ({h}, {w}): sizes must be positive")
+        g = math.gcd(h, w)
+        m = min(H0 // (h // g), W0 // (w // g))
+        rh, rw = m * (h // g), m * (w // g)
+        return _crop_offset(H0, rh), _crop_offset(W0, rw), rh, rw
+
+    def check(self, H0: int, W0: int, h: int, w: int) -> None:
+        """Everything `ebsdvae_resample_patterns` refuses for these sizes; raises ValueError."""
+        if not (0 < h <= MAX_RESAMPLED_SIDE and 0 < w <= MAX_RESAMPLED_SIDE):
+            raise ValueError(f"the output ({h}, {w}) must lie within "
+                             f"({MAX_RESAMPLED_SIDE}, {MAX_RESAMPLED_SIDE})")
+        top, left, rh, rw = self.window(H0, W0, h, w)
+        if top < 0 or left < 0 or rh < 1 or rw < 1 or top + rh > H0 or left + rw > W0:
+            raise ValueError(f"the region {(top, left, rh, rw)} leaves the ({H0}, {W0}) patterns")
+        if rh < h or rw < w:
+            raise ValueError(f"a ({rh}, {rw}) region is smaller than the ({h}, {w}) output: "
+                             "the resample bins down, it does not upsample")
+        if rh > MAX_RESAMPLE_FACTOR * h or rw > MAX_RESAMPLE_FACTOR * w:
+            raise ValueError(f"a ({rh}, {rw}) region onto ({h}, {w}) is a factor above "
+                             f"{MAX_RESAMPLE_FACTOR}")
+
+    def _on(self, device: torch.device, rh: int, rw: int, h: int, w: int):
+        """(ystart, ywts, ytaps, xstart, xwts, xtaps) on `device`, built and uploaded once."""
+        key = (device, rh, rw, h, w)
+        st = self._device_state.get(key)
+        if st is None:
+            st = ()
+            for R, O in ((rh, h), (rw, w)):
+                start, wts = resample_axis(R, O)
+                st += (torch.from_numpy(start).to(device), torch.from_numpy(wts).to(device),
+                       wts.shape[1])
+            self._device_state[key] = st
+        return st
+
+
+def resample_denominator(rh: int, rw: int, h: int, w: int, divisor: float = 1.0) -> np.float32:
+    """float32((rh / h) (rw / w) divisor), computed in float64: what the weighted sum of a
+    resampled pixel is divided by."""
+    return np.float32((float(rh) / float(h)) * (float(rw) / float(w)) * float(divisor))
+
+
+def resample_patterns(raw, image_size=(128, 128), resample: DetectorResample | None = None,
+                      divisor: float = 1.0, device="cuda", out: torch.Tensor | None = None):
+    """Detector binning on the device: raw (B, H0, W0) or (H0, W0) patterns (uint8, float32 or
+    float64, host or device) -> (B, 1, h, w) float32, the area mean of `resample`'s region
+    (default: `DetectorResample()`, the centred largest window) on the (h, w) grid, divided by
+    `divisor` (255 gives ToTensor's scale for uint8 data, what `ingest_patterns_u8` writes)
+    (`ebsdvae_resample_patterns`, csrc/resample.hip).  Non-finite source values count as 0.
+    Sizes are checked before anything touches the device; the tables are uploaded once per
+    (resample, geometry, device).  No CPU fallback."""
+    if resample is None:
+        resample = DetectorResample()
+    elif not isinstance(resample, DetectorResample):
+        raise TypeError(f"resample must be a DetectorResample, got {type(resample).__name__}")
+    t = torch.as_tensor(raw)
+    if t.dtype not in _SRC_CODES:
+        raise TypeError(f"resample_patterns needs uint8, float32 or float64 patterns, got {t.dtype}")
+    if t.ndim == 2:
+        t = t.unsqueeze(0)
+    if t.ndim != 3:
+        raise ValueError(f"patterns must be (B, H, W), got {tuple(t.shape)}")
+    B, H0, W0 = t.shape
+    h, w = (int(v) for v in image_size)
+    resample.check(H0, W0, h, w)
+    divisor = float(divisor)
+    if not (divisor > 0.0 and math.isfinite(divisor)):
+        raise ValueError(f"divisor must be a positive finite number, got {divisor}")
+    if out is not None and (out.numel() != B * h * w or not out.is_contiguous()):
+        raise ValueError(f"out must be a contiguous ({B}, 1, {h}, {w}) tensor, got {tuple(out.shape)}")
+    t = t.to(device, non_blocking=True).contiguous()
+    if not t.is_cuda:
+        raise RuntimeError("resample_patterns needs a ROCm device (no CPU fallback)")
+    top, left, rh, rw = resample.window(H0, W0, h, w)
+    ys, yw, yt, xs, xw, xt = resample._on(t.device, rh, rw, h, w)
+    if out is None:
+        out = torch.empty(B, 1, h, w, dtype=torch.float32, device=t.device)
+    N.call("ebsdvae_resample_patterns", t.data_ptr(), _SRC_CODES[t.dtype], B, H0, W0, top, left,
+           rh, rw, h, w, ys.data_ptr(), N.ptr(yw), yt, xs.data_ptr(), N.ptr(xw), xt,
+           float(resample_denominator(rh, rw, h, w, divisor)), N.ptr(out), N.stream(t.device))
+    return out
+
+
+def check_resampled_correction(correction: PatternCorrection, resample: DetectorResample,
+                               H0: int, W0: int, h: int, w: int) -> None:
+    """The size checks of `correct_patterns(..., resample=resample)`: the resample's own, the
+    correction's on the (h, w) patterns it then sees, and the static background, which stays at
+    detector shape (H0, W0) and, under "divide", must be positive inside the region."""
+    resample.check(H0, W0, h, w)
+    bg = correction.static_background
+    if bg is not None:
+        if bg.shape != (H0, W0):
+            raise ValueError(f"static_background is {bg.shape}, the patterns are ({H0}, {W0})")
+        if correction.static_mode == "divide":
+            t, l, rh, rw = resample.window(H0, W0, h, w)
+            if not (bg[t:t + rh, l:l + rw] > 0).all():
+                raise ValueError("static_mode 'divide' needs a background that is positive "
+                                 "everywhere inside the resampled region")
+    if correction.dynamic_sigma is not None:
+        r = int(4.0 * correction.dynamic_sigma + 0.5)
+        if r > min(h, w):
+            raise ValueError(f"dynamic_sigma={correction.dynamic_sigma} (in output pixels) gives a "
+                             f"blur radius of {r}, more than the output's smaller side {min(h, w)}")
+
+
+def _resampled_background(correction: PatternCorrection, resample: DetectorResample,
+                          device: torch.device, H0: int, W0: int, h: int, w: int):
+    """The static background binned as the patterns are (float32, divisor 1), (h, w) on
+    `device`; computed once per (correction, device, geometry).  None without a background."""
+    if correction.static_background is None:
+        return None
+    key = ("resampled", device, resample.window(H0, W0, h, w), h, w)
+    bg = correction._device_state.get(key)
+    if bg is None:
+        full = torch.from_numpy(correction.static_background.copy())[None]
+        bg = resample_patterns(full, (h, w), resample, 1.0, device).view(h, w)
+        correction._device_state[key] = bg
+    return bg
+
+
 def correct_patterns(raw, image_size=(128, 128), correction: PatternCorrection | None = None,
-                     device="cuda", out: torch.Tensor | None = None):
+                     device="cuda", out: torch.Tensor | None = None,
+                     resample: DetectorResample | None = None,
+                     intermediate: torch.Tensor | None = None):
     """Background-corrected ingest on the device: raw (B, H0, W0) detector patterns (uint8,
     float32 or float64, host or device) -> (B, 1, h, w) float32 in [0, 1]: centre crop (no
     padding), `correction`'s static and dynamic steps, per-pattern rescale
     (`ebsdvae_correct_patterns`, csrc/correct.hip).  Float sources are raw intensities of any
     scale.  Shapes and sizes are checked before anything touches the device; the background and
-    the taps are uploaded once per (correction, device)."""
+    the taps are uploaded once per (correction, device).
+
+    With `resample` (a `DetectorResample`) the patterns are binned to (h, w) first, in place of
+    the crop: resample (`resample_patterns`, divisor 1, into a float32 intermediate), static,
+    dynamic, rescale.  `correction.static_background` stays at detector shape (H0, W0) and is
+    binned once through the same kernel; under "divide" it must be positive inside the region.
+    `dynamic_sigma` is then in output pixels.  `intermediate` may supply the float32 buffer of
+    at least B h w elements the binned patterns pass through."""
     if not isinstance(correction, PatternCorrection):
         raise TypeError(f"correction must be a PatternCorrection, got {type(correction).__name__}")
+    if resample is not None:
+        return _correct_resampled(raw, image_size, correction, device, out, resample, intermediate)
     t = torch.as_tensor(raw)
     if t.dtype not in _SRC_CODES:
         raise TypeError(f"correct_patterns needs uint8, float32 or float64 patterns, got {t.dtype}")
@@ -247,6 +439,47 @@ def correct_patterns(raw, image_size=(128, 128), correction: PatternCorrection |
     nbytes = N.call("ebsdvae_correct_patterns_work", B, h, w)
     work = torch.empty(nbytes, dtype=torch.uint8, device=t.device) if nbytes else None
     N.call("ebsdvae_correct_patterns", t.data_ptr(), _SRC_CODES[t.dtype], B, H0, W0, h, w,
+           N.ptr(bg), correction.static_code, N.ptr(taps), radius, correction.dynamic_code,
+           N.ptr(out), work.data_ptr() if work is not None else None, N.stream(t.device))
+    return out
+
+
+def _correct_resampled(raw, image_size, correction, device, out, resample, intermediate):
+    """`correct_patterns` with a `DetectorResample`: bin to (h, w), then the correction kernel on
+    the binned patterns (its crop is the identity) with the binned background."""
+    if not isinstance(resample, DetectorResample):
+        raise TypeError(f"resample must be a DetectorResample, got {type(resample).__name__}")
+    t = torch.as_tensor(raw)
+    if t.dtype not in _SRC_CODES:
+        raise TypeError(f"correct_patterns needs uint8, float32 or float64 patterns, got {t.dtype}")
+    if t.ndim == 2:
+        t = t.unsqueeze(0)
+    if t.ndim != 3:
+        raise ValueError(f"patterns must be (B, H, W), got {tuple(t.shape)}")
+    B, H0, W0 = t.shape
+    h, w = (int(v) for v in image_size)
+    check_resampled_correction(correction, resample, H0, W0, h, w)
+    if out is not None and (out.numel() != B * h * w or not out.is_contiguous()):
+        raise ValueError(f"out must be a contiguous ({B}, 1, {h}, {w}) tensor, got {tuple(out.shape)}")
+    t = t.to(device, non_blocking=True).contiguous()
+    if not t.is_cuda:
+        raise RuntimeError("correct_patterns needs a ROCm device (no CPU fallback)")
+    if intermediate is None:
+        mid = torch.empty(B, 1, h, w, dtype=torch.float32, device=t.device)
+    else:
+        if not (intermediate.is_cuda and intermediate.dtype == torch.float32
+                and intermediate.is_contiguous() and intermediate.numel() >= B * h * w):
+            raise ValueError(f"intermediate must be a contiguous float32 device tensor of at least "
+                             f"{B} ({h}, {w}) patterns, got {tuple(intermediate.shape)}")
+        mid = intermediate.view(-1)[:B * h * w].view(B, 1, h, w)
+    resample_patterns(t, (h, w), resample, 1.0, t.device, out=mid)
+    bg = _resampled_background(correction, resample, t.device, H0, W0, h, w)
+    _, taps, radius = correction._on(t.device)
+    if out is None:
+        out = torch.empty(B, 1, h, w, dtype=torch.float32, device=t.device)
+    nbytes = N.call("ebsdvae_correct_patterns_work", B, h, w)
+    work = torch.empty(nbytes, dtype=torch.uint8, device=t.device) if nbytes else None
+    N.call("ebsdvae_correct_patterns", mid.data_ptr(), _SRC_CODES[torch.float32], B, h, w, h, w,
            N.ptr(bg), correction.static_code, N.ptr(taps), radius, correction.dynamic_code,
            N.ptr(out), work.data_ptr() if work is not None else None, N.stream(t.device))
     return out

@@ -19,6 +19,8 @@ path: same `IndexerConfig` and `DiffractionPatternIndexer` API and call contract
   `ScanIndexResult` of numpy arrays (latice/index/scan.py).  Raw detector scans take
   `correction=PatternCorrection(...)`: the ingest is then `correct_patterns` (static and
   dynamic background, rescale); `scan_background` streams a scan into its mean pattern.
+  `resample=DetectorResample(...)` bins detector-size patterns to the model's input size in
+  front of either ingest (`resample_patterns`, csrc/resample.hip).
   `neighbour_average=NeighbourAverage(...)` averages every transformed pattern with its
   neighbours on the scan grid between ingest and encoder; a host scan then streams through a
   device ring of transformed patterns (latice/index/scan.py `neighbour_schedule`).
@@ -34,10 +36,11 @@ import numpy as np
 import torch
 from pydantic.dataclasses import dataclass
 
-from latice.data_module import (DPDataModule, NeighbourAverage, PatternCorrection,
-                                PatternTransform, accumulate_patterns, average_neighbour_range,
+from latice.data_module import (DetectorResample, DPDataModule, NeighbourAverage,
+                                PatternCorrection, PatternTransform, accumulate_patterns,
+                                average_neighbour_range, check_resampled_correction,
                                 correct_patterns, create_default_transform, ingest_patterns,
-                                ingest_patterns_u8)
+                                ingest_patterns_u8, resample_patterns)
 from latice.index.faiss_db import (MAX_K, FaissLatentVectorDatabase,
                                    FaissLatentVectorDatabaseConfig, LatentIndexResult,
                                    OrientationResult)
@@ -82,10 +85,25 @@ def _default_db(dimension: int, device: torch.device):
     return ChromaLatentVectorDatabase(dimension=dimension)
 
 
-def _ingest_staged(raw, out, code, correction, size, dev):
+def _ingest_staged(raw, out, code, correction, size, dev, resample=None, mid=None):
     """One staged batch of a host scan -> transformed patterns in `out`: the corrected ingest
-    with a `correction`, else the plain one of the staging dtype `code`."""
-    if correction is not None:
+    with a `correction`, else the plain one of the staging dtype `code`.  With a `resample` the
+    detector patterns are binned to `size` first: uint8 straight into `out` at ToTensor's scale,
+    float data into the scan's intermediate `mid` and through the plain ingest at equal size
+    (the DPdataset transform's clamp and truncation), a corrected scan through `mid` inside
+    `correct_patterns`."""
+    if resample is not None:
+        if correction is not None:
+            correct_patterns(raw, size, correction, dev, out=out, resample=resample,
+                             intermediate=mid)
+        elif code == SCAN_U8:
+            resample_patterns(raw, size, resample, 255.0, dev, out=out)
+        else:
+            m = raw.shape[0]
+            binned = mid.view(-1)[:m * size[0] * size[1]].view(m, size[0], size[1])
+            resample_patterns(raw, size, resample, 1.0, dev, out=binned)
+            ingest_patterns(binned, size, dev, out=out)
+    elif correction is not None:
         correct_patterns(raw, size, correction, dev, out=out)
     elif code == SCAN_U8:
         ingest_patterns_u8(raw, size, dev, out=out)
@@ -187,7 +205,8 @@ class DiffractionPatternIndexer:
                    max_iterations: int = 3, batch_size: int | None = None,
                    return_candidates: bool = False,
                    correction: PatternCorrection | None = None,
-                   neighbour_average: NeighbourAverage | None = None) -> ScanIndexResult:
+                   neighbour_average: NeighbourAverage | None = None,
+                   resample: DetectorResample | None = None) -> ScanIndexResult:
         """A whole scan in, an orientation map out, everything between on the device.
 
         `patterns` is a path to a .npy file (memory-mapped), a numpy array / memmap
@@ -209,7 +228,22 @@ class DiffractionPatternIndexer:
         transformed patterns, so a device tensor may take it too.  A host scan is ingested, each
         pattern once, into a device ring of batch_size + 2 (hr cols + hc) transformed patterns;
         the outputs whose neighbours have all arrived are averaged straight into the encoder's
-        batch buffer, in chunks of at most batch_size."""
+        batch buffer, in chunks of at most batch_size.
+
+        With `resample` (a `DetectorResample`) a host scan of detector-size patterns is binned
+        to the model's input size on the device, in front of everything else
+        (`resample_patterns`: the area mean of the resample's region): uint8 patterns straight
+        into the encoder's batch buffer (or the ring) at v / 255, float patterns through one
+        intermediate and the plain ingest at equal size, and with a `correction` through that
+        intermediate into `correct_patterns`, whose static background stays at detector shape
+        and whose `dynamic_sigma` is in output pixels.  The intermediate is allocated once per
+        scan.  A device tensor is already transformed and cannot take one."""
+        if resample is not None:
+            if not isinstance(resample, DetectorResample):
+                raise TypeError(f"resample must be a DetectorResample, got {type(resample).__name__}")
+            if torch.is_tensor(patterns):
+                raise ValueError("a tensor scan is already transformed: `resample` applies to "
+                                 "host scans of raw detector patterns")
         if neighbour_average is not None and not isinstance(neighbour_average, NeighbourAverage):
             raise TypeError("neighbour_average must be a NeighbourAverage, got "
                             f"{type(neighbour_average).__name__}")
@@ -243,7 +277,12 @@ class DiffractionPatternIndexer:
         else:
             patterns = open_scan(patterns)
             items = scan_batches(patterns, batch_size)
-            if correction is not None:
+            if resample is not None and correction is not None:
+                check_resampled_correction(correction, resample, *patterns.shape[1:],
+                                           *self.config.image_size)
+            elif resample is not None:
+                resample.check(*patterns.shape[1:], *self.config.image_size)
+            elif correction is not None:
                 correction.check(*patterns.shape[1:], *self.config.image_size)
             n, dev = patterns.shape[0], self.device
         if neighbour_average is not None:
@@ -287,9 +326,10 @@ class DiffractionPatternIndexer:
                 self.db.index_latents(self.model.encode_mu(patterns[s:e]), out=res.slice(s, e), **kw)
         elif n and neighbour_average is not None:
             staging = self._stream_scan_averaged(patterns, items, batch_size, dev, res, kw,
-                                                 correction, neighbour_average)
+                                                 correction, neighbour_average, resample)
         elif n:
-            staging = self._stream_scan(patterns, items, batch_size, dev, res, kw, correction)
+            staging = self._stream_scan(patterns, items, batch_size, dev, res, kw, correction,
+                                        resample)
 
         host = buf.cpu().numpy()     # the one device-to-host copy (and the only host wait)
         del staging                  # every copy-stream buffer outlived its last consumer
@@ -301,26 +341,40 @@ class DiffractionPatternIndexer:
                                candidate_indices=h.get("cand_idx"),
                                candidate_scores=h.get("cand_scores"))
 
-    def _stream_scan(self, patterns, items, batch_size, dev, res, kw, correction=None):
+    def _resample_intermediate(self, n, batch_size, code, correction, resample, dev):
+        """The float32 buffer binned patterns pass through on their way to the plain float
+        ingest or the correction: one per scan, batch_size patterns.  None where no path uses
+        one (no resample, or uint8 without a correction)."""
+        if resample is None or (correction is None and code == SCAN_U8):
+            return None
+        h, w = self.config.image_size
+        with torch.cuda.device(dev):
+            return torch.empty(min(batch_size, n), 1, h, w, dtype=torch.float32, device=dev)
+
+    def _stream_scan(self, patterns, items, batch_size, dev, res, kw, correction=None,
+                     resample=None):
         """index_scan over a host scan: every staged batch is ingested into one (B, 1, h, w)
         buffer (the corrected ingest with a `correction`, else the plain one of the staging
-        dtype), then encoded and indexed into its rows of `res`."""
+        dtype; binned first with a `resample`), then encoded and indexed into its rows of
+        `res`."""
         code = items[0][2]
         h, w = self.config.image_size
         with torch.cuda.device(dev):
             x = torch.empty(min(batch_size, patterns.shape[0]), 1, h, w, dtype=torch.float32,
                             device=dev)
+        mid = self._resample_intermediate(patterns.shape[0], batch_size, code, correction,
+                                          resample, dev)
 
         def ingest(raw):
-            _ingest_staged(raw, x[:raw.shape[0]], code, correction, (h, w), dev)
+            _ingest_staged(raw, x[:raw.shape[0]], code, correction, (h, w), dev, resample, mid)
 
         def index(s, e):
             self.db.index_latents(self.model.encode_mu(x[:e - s]), out=res.slice(s, e), **kw)
 
-        return self._stream_batches(patterns, items, batch_size, dev, ingest, index) + (x,)
+        return self._stream_batches(patterns, items, batch_size, dev, ingest, index) + (x, mid)
 
     def _stream_scan_averaged(self, patterns, items, batch_size, dev, res, kw, correction,
-                              neighbour_average):
+                              neighbour_average, resample=None):
         """index_scan over a host scan with neighbour averaging: every staged batch is ingested,
         once, into its slots of a ring of transformed patterns (`neighbour_schedule`; in two
         parts where it passes the ring's end); the outputs that are complete after it are
@@ -335,6 +389,7 @@ class DiffractionPatternIndexer:
         with torch.cuda.device(dev):
             ring = torch.empty(schedule.ring_cap, 1, h, w, dtype=torch.float32, device=dev)
             x = torch.empty(min(batch_size, n), 1, h, w, dtype=torch.float32, device=dev)
+        mid = self._resample_intermediate(n, batch_size, code, correction, resample, dev)
         steps = iter(schedule.steps)    # one per staged batch, in the order of `items`
         current = []
 
@@ -343,7 +398,7 @@ class DiffractionPatternIndexer:
             current[:] = [step]
             for a, b, slot in step.ingest:
                 _ingest_staged(raw[a - step.start:b - step.start], ring[slot:slot + b - a], code,
-                               correction, (h, w), dev)
+                               correction, (h, w), dev, resample, mid)
 
         def index(s, e):
             step, = current
@@ -352,7 +407,7 @@ class DiffractionPatternIndexer:
                 average_neighbour_range(ring, neighbour_average, a, b - a, x)
                 self.db.index_latents(self.model.encode_mu(x[:b - a]), out=res.slice(a, b), **kw)
 
-        return self._stream_batches(patterns, items, batch_size, dev, ingest, index) + (ring, x)
+        return self._stream_batches(patterns, items, batch_size, dev, ingest, index) + (ring, x, mid)
 
     def _stream_batches(self, patterns, items, batch_size, dev, ingest, then=None):
         """The host half of a streamed scan: batch i is copied from the scan into pinned buffer

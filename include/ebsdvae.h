@@ -580,6 +580,34 @@ size_t ebsdvae_correct_patterns_work(int B, int out_h, int out_w);
 int ebsdvae_accumulate_patterns(const void* src, int src_dtype, int B, int H0, int W0,
                                 double* acc, ebsdvae_stream_t stream);
 
+/* ---- detector resampling ("Detector resampling") ----------------
+ * Exact area-mean resample (a box filter with fractional pixel overlap) of the region
+ * (top, left, rh, rw) of every raw detector pattern src (B, H0, W0) (src_dtype 0 = float64,
+ * 1 = float32, 2 = uint8) to dst (B, 1, out_h, out_w): downsampling or identity, by a factor of
+ * 1 to 8 per axis, independently (out_h <= rh <= 8 out_h, out_w <= rw <= 8 out_w).  Per pattern:
+ *   u[y][x] = float32(src[top + y][left + x]), non-finite -> 0;
+ *   r[y][j] = sum over t < xtaps of xwts[j][t] * u[y][xstart[j] + t];
+ *   S[i][j] = sum over t < ytaps of ywts[i][t] * r[ystart[i] + t][j];
+ *   out[i][j] = S[i][j] / denom, one true float32 division.
+ * Both sums are float32 fma chains from 0, t ascending.  The tables are device arrays, per axis
+ * with R the region's size and O the output's: start (O,) int32, the first tap of an output
+ * relative to the region, non-decreasing, and wts (O, taps) float32, the overlap of source pixel
+ * start[j] + t with output pixel j in output pixels,
+ *   max(0, min((j + 1) R, (x + 1) O) - max(j R, x O)) / O,
+ * nonzero for at most ceil(R / O) + 1 consecutive pixels.  A row of wts may be padded with zero
+ * weights in front or behind (fma(0, u, s) = s: the padding leaves the chain's bits unchanged); a
+ * tap position outside the region is never read past the pattern, and needs a zero weight.  denom
+ * is (rh / out_h) (rw / out_w) times the divisor of the source's scale (255 for ToTensor's
+ * uint8 / 255, else 1), rounded to float32 by the caller.  A pattern's output depends on the
+ * pattern, the region and the sizes alone.
+ * Nonzero, and nothing written, for a null pointer, a region that leaves the pattern,
+ * rh < out_h, rw < out_w or a factor above 8, out_h or out_w outside 1..256, ytaps or xtaps
+ * outside 1..9, or a denom that is not positive and finite.  No scratch, no atomics. */
+int ebsdvae_resample_patterns(const void* src, int src_dtype, int B, int H0, int W0, int top,
+                              int left, int rh, int rw, int out_h, int out_w, const int* ystart,
+                              const float* ywts, int ytaps, const int* xstart, const float* xwts,
+                              int xtaps, float denom, float* dst, ebsdvae_stream_t stream);
+
 /* ---- neighbour pattern averaging ("Neighbour pattern averaging") --
  * The scan's rows * cols transformed patterns T (h x w float32 each, values in [0, 1], what the
  * ingests above write) lie on a grid in row-major order, pattern p at (i, j) = (p / cols,
