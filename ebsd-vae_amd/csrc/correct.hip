@@ -27,6 +27,7 @@
 
 #include "common.h"
 #include "crop.h"
+#include "pattern_src.h"
 #include "../../include/ebsdvae.h"
 
 namespace ev {
@@ -51,8 +52,7 @@ struct CorrArgs {
 template <typename T>
 EV_DEVINL float load_static(const T* __restrict__ pat, const CorrArgs& a, int y, int x) {
   const size_t o = (size_t)(y + a.top) * a.W0 + (x + a.left);
-  float v = (float)pat[o];
-  if (!(fabsf(v) <= 3.4028235e38f)) v = 0.f;   // NaN, +-inf
+  float v = finite_or_zero((float)pat[o]);
   if (a.smode == 1) v = v - a.bg[o];
   else if (a.smode == 2) v = v / a.bg[o];
   return v;
@@ -371,10 +371,8 @@ extern "C" int ebsdvae_correct_patterns(const void* src, int src_dtype, int B, i
   a.bg = static_bg, a.taps = taps;
   a.smode = static_mode, a.dmode = dynamic_mode, a.radius = dynamic_mode ? radius : 0;
   const hipStream_t st = (hipStream_t)stream;
-  bool ok;
-  if (src_dtype == 0) ok = launch_correct((const double*)src, a, B, dst, (float*)work, st);
-  else if (src_dtype == 1) ok = launch_correct((const float*)src, a, B, dst, (float*)work, st);
-  else ok = launch_correct((const unsigned char*)src, a, B, dst, (float*)work, st);
+  bool ok = false;
+  evh::with_src(src, src_dtype, [&](auto p) { ok = launch_correct(p, a, B, dst, (float*)work, st); });
   if (!ok) {
     (void)hipGetLastError();
     evh::set_error("correct_patterns: the device refused the LDS a %dx%d window needs", out_h, out_w);
@@ -393,12 +391,8 @@ extern "C" int ebsdvae_accumulate_patterns(const void* src, int src_dtype, int B
   const int npx = H0 * W0;
   const dim3 grid((unsigned)((npx + 255) / 256));
   const hipStream_t st = (hipStream_t)stream;
-  if (src_dtype == 0)
-    hipLaunchKernelGGL(accumulate_kernel<double>, grid, dim3(256), 0, st, (const double*)src, B, npx, acc);
-  else if (src_dtype == 1)
-    hipLaunchKernelGGL(accumulate_kernel<float>, grid, dim3(256), 0, st, (const float*)src, B, npx, acc);
-  else
-    hipLaunchKernelGGL(accumulate_kernel<unsigned char>, grid, dim3(256), 0, st,
-                       (const unsigned char*)src, B, npx, acc);
+  evh::with_src(src, src_dtype, [&](auto p) {
+    hipLaunchKernelGGL(accumulate_kernel<evh::elem_t<decltype(p)>>, grid, dim3(256), 0, st, p, B, npx, acc);
+  });
   return evh::check_launch("accumulate_patterns");
 }

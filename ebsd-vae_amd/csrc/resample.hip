@@ -30,6 +30,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "pattern_src.h"
 #include "../../include/ebsdvae.h"
 
 namespace ev {
@@ -77,8 +78,6 @@ static inline size_t rs_lds_bytes(int esize, const RsArgs& a, int cw, int* pitch
   return (size_t)*xoff + (size_t)a.cap_rows * (cw | 1) * 4 + (size_t)cw * 4 +
          (size_t)cw * a.xtaps * 4 + (size_t)kRsBand * 4 + (size_t)kRsBand * a.ytaps * 4;
 }
-
-EV_DEVINL float rs_finite(float v) { return fabsf(v) <= 3.4028235e38f ? v : 0.f; }   // NaN, +-inf
 
 // offset (0..3) of a uint8 row in its first aligned word
 EV_DEVINL int rs_misalign(const void* src, size_t element) {
@@ -247,7 +246,7 @@ __global__ __launch_bounds__(kRsThreads) void resample_kernel(const T* __restric
         } else {
           const T* line = reinterpret_cast<const T*>(lds + (size_t)y * a.pitch);
 #pragma unroll
-          for (int t = 0; t < XT; ++t) u[t] = rs_finite((float)line[min(s + t, cols - 1)]);
+          for (int t = 0; t < XT; ++t) u[t] = finite_or_zero((float)line[min(s + t, cols - 1)]);
         }
         float acc = 0.f;
 #pragma unroll
@@ -326,8 +325,6 @@ extern "C" int ebsdvae_resample_patterns(const void* src, int src_dtype, int B, 
   a.cap_rows = rs_span(out_h < kRsBand ? out_h : kRsBand, rh, out_h, ytaps);
   a.cw = a.cap_cols = a.pitch = a.xoff = 0;
   const hipStream_t st = (hipStream_t)stream;
-  if (src_dtype == 0) launch_resample((const double*)src, B, a, dst, st);
-  else if (src_dtype == 1) launch_resample((const float*)src, B, a, dst, st);
-  else launch_resample((const unsigned char*)src, B, a, dst, st);
+  evh::with_src(src, src_dtype, [&](auto p) { launch_resample(p, B, a, dst, st); });
   return evh::check_launch("resample_patterns");
 }

@@ -3,7 +3,8 @@
 Modules this package replaces (same names, classes and call contracts as the reference):
 `latice.model`, `latice.lightning_module`, `latice.data_module`, `latice.index.dp_indexer`,
 `latice.index.faiss_db`.  Their compute runs in libebsdvae.so (HIP, gfx950) through
-`latice._native`.
+`latice._native`.  `latice.patterns` holds the device pattern stages the reference does not
+have (batched ingest, background correction, detector binning, neighbour averaging).
 
 Modules it does not replace -- `latice.utils` (plotting, IPF colour keys), the Chroma vector
 database `latice.index.chroma_db`, the legacy `latice.index.latent_embedding` -- are taken

@@ -15,15 +15,16 @@ path: same `IndexerConfig` and `DiffractionPatternIndexer` API and call contract
   default one (the reference loops per pattern, :149-163).
 * `index_scan` has no counterpart in the reference: a whole scan (a .npy path, a host array of
   float or uint8 patterns, or a transformed device tensor) streams through pinned staging
-  buffers, ingest, `encode_mu` and `db.index_latents`, and comes back as one
-  `ScanIndexResult` of numpy arrays (latice/index/scan.py).  Raw detector scans take
-  `correction=PatternCorrection(...)`: the ingest is then `correct_patterns` (static and
-  dynamic background, rescale); `scan_background` streams a scan into its mean pattern.
-  `resample=DetectorResample(...)` bins detector-size patterns to the model's input size in
-  front of either ingest (`resample_patterns`, csrc/resample.hip).
-  `neighbour_average=NeighbourAverage(...)` averages every transformed pattern with its
-  neighbours on the scan grid between ingest and encoder; a host scan then streams through a
-  device ring of transformed patterns (latice/index/scan.py `neighbour_schedule`).
+  buffers (`_stream_batches`), the scan's ingest plan, `encode_mu` and `db.index_latents`,
+  and comes back as one `ScanIndexResult` of numpy arrays (latice/index/scan.py).  The plan
+  is a `latice.patterns.ScanIngest`, built once per scan: it checks `correction=
+  PatternCorrection(...)` (raw detector scans: static and dynamic background, rescale) and
+  `resample=DetectorResample(...)` (detector-size patterns binned to the model's input size
+  in front of either ingest) against the scan and fixes which device stages a staged batch
+  runs through.  `neighbour_average=NeighbourAverage(...)` averages every transformed pattern
+  with its neighbours on the scan grid between ingest and encoder; a host scan then streams
+  through a device ring of transformed patterns (latice/index/scan.py `neighbour_schedule`).
+  `scan_background` streams a scan into its mean pattern, the usual static background.
 """
 from __future__ import annotations
 
@@ -36,17 +37,15 @@ import numpy as np
 import torch
 from pydantic.dataclasses import dataclass
 
-from latice.data_module import (DetectorResample, DPDataModule, NeighbourAverage,
-                                PatternCorrection, PatternTransform, accumulate_patterns,
-                                average_neighbour_range, check_resampled_correction,
-                                correct_patterns, create_default_transform, ingest_patterns,
-                                ingest_patterns_u8, resample_patterns)
+from latice.data_module import DPDataModule, PatternTransform, create_default_transform
 from latice.index.faiss_db import (MAX_K, FaissLatentVectorDatabase,
                                    FaissLatentVectorDatabaseConfig, LatentIndexResult,
                                    OrientationResult)
 from latice.index.scan import (SCAN_F32, SCAN_F64, SCAN_U8, ScanIndexResult, neighbour_schedule,
-                               open_scan, scan_batches)
+                               open_scan, scan_batches, scan_dtype_code)
 from latice.model import VariationalAutoEncoder
+from latice.patterns import (DetectorResample, NeighbourAverage, PatternCorrection, ScanIngest,
+                             accumulate_patterns, average_neighbour_range)
 
 logger = logging.getLogger(__name__)
 
@@ -85,30 +84,50 @@ def _default_db(dimension: int, device: torch.device):
     return ChromaLatentVectorDatabase(dimension=dimension)
 
 
-def _ingest_staged(raw, out, code, correction, size, dev, resample=None, mid=None):
-    """One staged batch of a host scan -> transformed patterns in `out`: the corrected ingest
-    with a `correction`, else the plain one of the staging dtype `code`.  With a `resample` the
-    detector patterns are binned to `size` first: uint8 straight into `out` at ToTensor's scale,
-    float data into the scan's intermediate `mid` and through the plain ingest at equal size
-    (the DPdataset transform's clamp and truncation), a corrected scan through `mid` inside
-    `correct_patterns`."""
-    if resample is not None:
-        if correction is not None:
-            correct_patterns(raw, size, correction, dev, out=out, resample=resample,
-                             intermediate=mid)
-        elif code == SCAN_U8:
-            resample_patterns(raw, size, resample, 255.0, dev, out=out)
-        else:
-            m = raw.shape[0]
-            binned = mid.view(-1)[:m * size[0] * size[1]].view(m, size[0], size[1])
-            resample_patterns(raw, size, resample, 1.0, dev, out=binned)
-            ingest_patterns(binned, size, dev, out=out)
-    elif correction is not None:
-        correct_patterns(raw, size, correction, dev, out=out)
-    elif code == SCAN_U8:
-        ingest_patterns_u8(raw, size, dev, out=out)
-    else:
-        ingest_patterns(raw, size, dev, out=out)
+_NUMPY = {torch.float64: np.float64, torch.int64: np.int64, torch.float32: np.float32,
+          torch.int32: np.int32}
+
+
+def _check_raw_stage(name: str, stage, cls, patterns) -> None:
+    """An optional stage of index_scan that works on raw host patterns: its type, and that the
+    scan is not a tensor."""
+    if stage is None:
+        return
+    if not isinstance(stage, cls):
+        raise TypeError(f"{name} must be a {cls.__name__}, got {type(stage).__name__}")
+    if torch.is_tensor(patterns):
+        raise ValueError(f"a tensor scan is already transformed: `{name}` applies to "
+                         "host scans of raw detector patterns")
+
+
+def _result_buffer(n: int, k: int, candidates: bool, dev):
+    """The results of an n-pattern scan (k candidates per pattern if `candidates`) as views
+    of ONE device buffer, so one copy brings them all back.  Returns (the buffer, its layout
+    [(name, dtype, shape, byte offset, bytes)], the views as a `LatentIndexResult`)."""
+    # the 8-byte fields come first to keep every view aligned
+    fields = [("best", torch.float64, (n, 3)), ("row", torch.int64, (n,))]
+    fields += [("cand_idx", torch.int64, (n, k))] if candidates else []
+    fields += [("score", torch.float32, (n,)), ("success", torch.int32, (n,)),
+               ("n_similar", torch.int32, (n,))]
+    fields += [("cand_scores", torch.float32, (n, k))] if candidates else []
+    layout, end = [], 0
+    for name, dt, shape in fields:
+        nbytes = int(np.prod(shape)) * torch.empty((), dtype=dt).element_size()
+        layout.append((name, dt, shape, end, nbytes))
+        end += nbytes
+    buf = torch.empty(max(end, 8), dtype=torch.uint8, device=dev)
+    return buf, layout, LatentIndexResult(**{name: buf[o:o + nb].view(dt).view(shape)
+                                             for name, dt, shape, o, nb in layout})
+
+
+def _unpack_result(buf: torch.Tensor, layout) -> ScanIndexResult:
+    """The one device-to-host copy of a scan's results (and the host's only wait)."""
+    host = buf.cpu().numpy()
+    h = {name: host[o:o + nb].view(_NUMPY[dt]).reshape(shape) for name, dt, shape, o, nb in layout}
+    return ScanIndexResult(orientations=h["best"], success=h["success"].astype(bool),
+                           scores=h["score"], top_index=h["row"], n_similar=h["n_similar"],
+                           candidate_indices=h.get("cand_idx"),
+                           candidate_scores=h.get("cand_scores"))
 
 
 class DiffractionPatternIndexer:
@@ -238,21 +257,11 @@ class DiffractionPatternIndexer:
         intermediate into `correct_patterns`, whose static background stays at detector shape
         and whose `dynamic_sigma` is in output pixels.  The intermediate is allocated once per
         scan.  A device tensor is already transformed and cannot take one."""
-        if resample is not None:
-            if not isinstance(resample, DetectorResample):
-                raise TypeError(f"resample must be a DetectorResample, got {type(resample).__name__}")
-            if torch.is_tensor(patterns):
-                raise ValueError("a tensor scan is already transformed: `resample` applies to "
-                                 "host scans of raw detector patterns")
+        _check_raw_stage("resample", resample, DetectorResample, patterns)
         if neighbour_average is not None and not isinstance(neighbour_average, NeighbourAverage):
             raise TypeError("neighbour_average must be a NeighbourAverage, got "
                             f"{type(neighbour_average).__name__}")
-        if correction is not None:
-            if not isinstance(correction, PatternCorrection):
-                raise TypeError(f"correction must be a PatternCorrection, got {type(correction).__name__}")
-            if torch.is_tensor(patterns):
-                raise ValueError("a tensor scan is already transformed: `correction` applies to "
-                                 "host scans of raw detector patterns")
+        _check_raw_stage("correction", correction, PatternCorrection, patterns)
         top_n = top_n or self.config.top_n
         orientation_threshold = orientation_threshold or self.config.orientation_threshold
         batch_size = int(batch_size or self.config.batch_size)
@@ -277,143 +286,88 @@ class DiffractionPatternIndexer:
         else:
             patterns = open_scan(patterns)
             items = scan_batches(patterns, batch_size)
-            if resample is not None and correction is not None:
-                check_resampled_correction(correction, resample, *patterns.shape[1:],
-                                           *self.config.image_size)
-            elif resample is not None:
-                resample.check(*patterns.shape[1:], *self.config.image_size)
-            elif correction is not None:
-                correction.check(*patterns.shape[1:], *self.config.image_size)
             n, dev = patterns.shape[0], self.device
+            plan = ScanIngest(patterns.shape[1:], scan_dtype_code(patterns.dtype),
+                              self.config.image_size, dev, min(batch_size, n), correction, resample)
         if neighbour_average is not None:
             neighbour_average.check(n)
         k = min(top_n, self.db.get_count()) if return_candidates else 0
+        buf, layout, res = _result_buffer(n, k, return_candidates, dev)
 
-        # every result array is a view of ONE device buffer, so one copy brings them all
-        # back; the 8-byte fields come first to keep every view aligned
-        fields = [("best", torch.float64, (n, 3)), ("row", torch.int64, (n,))]
-        if return_candidates:
-            fields.append(("cand_idx", torch.int64, (n, k)))
-        fields += [("score", torch.float32, (n,)), ("success", torch.int32, (n,)),
-                   ("n_similar", torch.int32, (n,))]
-        if return_candidates:
-            fields.append(("cand_scores", torch.float32, (n, k)))
-        sizes = [int(np.prod(shape)) * torch.empty((), dtype=dt).element_size()
-                 for _, dt, shape in fields]
-        offsets = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
-        buf = torch.empty(max(int(offsets[-1]), 8), dtype=torch.uint8, device=dev)
+        def encode_index(x, a, b):
+            """Transformed patterns x of the scan's [a, b) -> their rows of the result."""
+            self.db.index_latents(self.model.encode_mu(x), out=res.slice(a, b), **kw)
 
-        def carve(raw, to_view):
-            return {name: to_view(raw[int(o):int(o) + sz], dt, shape)
-                    for (name, dt, shape), o, sz in zip(fields, offsets, sizes)}
+        def average_index(ring, x, chunks):
+            """Every chunk [a, b) averaged out of `ring` into x[:b - a], encoded and indexed."""
+            for a, b in chunks:
+                average_neighbour_range(ring, neighbour_average, a, b - a, x)
+                encode_index(x[:b - a], a, b)
 
         staging = None
-        res = LatentIndexResult(**carve(buf, lambda b, dt, shape: b.view(dt).view(shape)))
-
         if on_device and neighbour_average is not None and n:
             ring = patterns.contiguous()     # a resident scan is its own ring
             with torch.cuda.device(dev):
                 x = torch.empty((min(batch_size, n),) + tuple(ring.shape[1:]),
                                 dtype=torch.float32, device=dev)
-            for s in range(0, n, batch_size):
-                e = min(s + batch_size, n)
-                average_neighbour_range(ring, neighbour_average, s, e - s, x)
-                self.db.index_latents(self.model.encode_mu(x[:e - s]), out=res.slice(s, e), **kw)
+            average_index(ring, x, [(s, min(s + batch_size, n)) for s in range(0, n, batch_size)])
             staging = (ring, x)
         elif on_device:
             for s in range(0, n, batch_size):
                 e = min(s + batch_size, n)
-                self.db.index_latents(self.model.encode_mu(patterns[s:e]), out=res.slice(s, e), **kw)
+                encode_index(patterns[s:e], s, e)
         elif n and neighbour_average is not None:
-            staging = self._stream_scan_averaged(patterns, items, batch_size, dev, res, kw,
-                                                 correction, neighbour_average, resample)
+            staging = self._stream_scan_averaged(patterns, items, batch_size, dev, plan,
+                                                 neighbour_average, average_index)
         elif n:
-            staging = self._stream_scan(patterns, items, batch_size, dev, res, kw, correction,
-                                        resample)
+            staging = self._stream_scan(patterns, items, batch_size, dev, plan, encode_index)
 
-        host = buf.cpu().numpy()     # the one device-to-host copy (and the only host wait)
+        result = _unpack_result(buf, layout)     # the host's only wait
         del staging                  # every copy-stream buffer outlived its last consumer
-        np_dt = {torch.float64: np.float64, torch.int64: np.int64, torch.float32: np.float32,
-                 torch.int32: np.int32}
-        h = carve(host, lambda b, dt, shape: b.view(np_dt[dt]).reshape(shape))
-        return ScanIndexResult(orientations=h["best"], success=h["success"].astype(bool),
-                               scores=h["score"], top_index=h["row"], n_similar=h["n_similar"],
-                               candidate_indices=h.get("cand_idx"),
-                               candidate_scores=h.get("cand_scores"))
+        return result
 
-    def _resample_intermediate(self, n, batch_size, code, correction, resample, dev):
-        """The float32 buffer binned patterns pass through on their way to the plain float
-        ingest or the correction: one per scan, batch_size patterns.  None where no path uses
-        one (no resample, or uint8 without a correction)."""
-        if resample is None or (correction is None and code == SCAN_U8):
-            return None
-        h, w = self.config.image_size
-        with torch.cuda.device(dev):
-            return torch.empty(min(batch_size, n), 1, h, w, dtype=torch.float32, device=dev)
-
-    def _stream_scan(self, patterns, items, batch_size, dev, res, kw, correction=None,
-                     resample=None):
-        """index_scan over a host scan: every staged batch is ingested into one (B, 1, h, w)
-        buffer (the corrected ingest with a `correction`, else the plain one of the staging
-        dtype; binned first with a `resample`), then encoded and indexed into its rows of
-        `res`."""
-        code = items[0][2]
+    def _stream_scan(self, patterns, items, batch_size, dev, plan, encode_index):
+        """index_scan over a host scan: every staged batch goes through the scan's ingest `plan`
+        into one (B, 1, h, w) buffer, then is encoded and indexed into its rows of the result."""
         h, w = self.config.image_size
         with torch.cuda.device(dev):
             x = torch.empty(min(batch_size, patterns.shape[0]), 1, h, w, dtype=torch.float32,
                             device=dev)
-        mid = self._resample_intermediate(patterns.shape[0], batch_size, code, correction,
-                                          resample, dev)
+        return self._stream_batches(patterns, items, batch_size, dev,
+                                    lambda i, raw: plan.plan(raw, x[:raw.shape[0]]),
+                                    lambda i, s, e: encode_index(x[:e - s], s, e)) + (x,)
 
-        def ingest(raw):
-            _ingest_staged(raw, x[:raw.shape[0]], code, correction, (h, w), dev, resample, mid)
-
-        def index(s, e):
-            self.db.index_latents(self.model.encode_mu(x[:e - s]), out=res.slice(s, e), **kw)
-
-        return self._stream_batches(patterns, items, batch_size, dev, ingest, index) + (x, mid)
-
-    def _stream_scan_averaged(self, patterns, items, batch_size, dev, res, kw, correction,
-                              neighbour_average, resample=None):
+    def _stream_scan_averaged(self, patterns, items, batch_size, dev, plan, neighbour_average,
+                              average_index):
         """index_scan over a host scan with neighbour averaging: every staged batch is ingested,
-        once, into its slots of a ring of transformed patterns (`neighbour_schedule`; in two
-        parts where it passes the ring's end); the outputs that are complete after it are
-        averaged from the ring into the encoder's batch buffer, chunk by chunk, then encoded and
-        indexed into their rows of `res`.  All of it is work on the compute stream, in order:
-        the ring is overwritten only after the last averaging that reads the old patterns."""
-        code = items[0][2]
+        once, into its slots of a ring of transformed patterns (`neighbour_schedule`, one step
+        per batch; in two parts where it passes the ring's end); the outputs that are complete
+        after it are averaged from the ring into the encoder's batch buffer, chunk by chunk,
+        then encoded and indexed into their rows of the result.  All of it is work on the
+        compute stream, in order: the ring is overwritten only after the last averaging that
+        reads the old patterns."""
         h, w = self.config.image_size
         n = patterns.shape[0]
         hr, hc = neighbour_average.half
         schedule = neighbour_schedule(n, neighbour_average.scan_shape[1], hr, hc, batch_size)
+        steps = schedule.steps
         with torch.cuda.device(dev):
             ring = torch.empty(schedule.ring_cap, 1, h, w, dtype=torch.float32, device=dev)
             x = torch.empty(min(batch_size, n), 1, h, w, dtype=torch.float32, device=dev)
-        mid = self._resample_intermediate(n, batch_size, code, correction, resample, dev)
-        steps = iter(schedule.steps)    # one per staged batch, in the order of `items`
-        current = []
 
-        def ingest(raw):
-            step = next(steps)
-            current[:] = [step]
-            for a, b, slot in step.ingest:
-                _ingest_staged(raw[a - step.start:b - step.start], ring[slot:slot + b - a], code,
-                               correction, (h, w), dev, resample, mid)
+        def ingest(i, raw):
+            start = steps[i].start
+            for a, b, slot in steps[i].ingest:
+                plan.plan(raw[a - start:b - start], ring[slot:slot + b - a])
 
-        def index(s, e):
-            step, = current
-            assert (step.start, step.stop) == (s, e)
-            for a, b in step.ready:
-                average_neighbour_range(ring, neighbour_average, a, b - a, x)
-                self.db.index_latents(self.model.encode_mu(x[:b - a]), out=res.slice(a, b), **kw)
-
-        return self._stream_batches(patterns, items, batch_size, dev, ingest, index) + (ring, x, mid)
+        return self._stream_batches(patterns, items, batch_size, dev, ingest,
+                                    lambda i, s, e: average_index(ring, x, steps[i].ready)) + (ring, x)
 
     def _stream_batches(self, patterns, items, batch_size, dev, ingest, then=None):
         """The host half of a streamed scan: batch i is copied from the scan into pinned buffer
         i & 1, then to device buffer i & 1 on a copy stream, while the compute stream still
-        works on batch i - 1; `ingest(staged batch)` is the one consumer of the device buffer,
-        `then(start, stop)` whatever follows it on the compute stream.  Events order the two
+        works on batch i - 1; `ingest(i, staged batch)` is the one consumer of the device buffer,
+        `then(i, start, stop)` whatever follows it on the compute stream.  Events order the two
         streams in both directions; the host waits only for `copied[j]` (the copy out of the
         pinned buffer it is about to refill).  The staging buffers are returned: the caller
         keeps them alive until it has synchronised the compute stream, which has waited for
@@ -446,11 +400,11 @@ class DiffractionPatternIndexer:
                 copied[j] = torch.cuda.Event()
                 copied[j].record(copy)
                 compute.wait_event(copied[j])
-                ingest(staged[j][:m])
+                ingest(i, staged[j][:m])
                 ingested[j] = torch.cuda.Event()
                 ingested[j].record(compute)
                 if then is not None:
-                    then(s, e)
+                    then(i, s, e)
         return pinned, staged
 
     def scan_background(self, patterns, batch_size: int | None = None) -> np.ndarray:
@@ -467,7 +421,7 @@ class DiffractionPatternIndexer:
             raise RuntimeError("scan_background needs a ROCm device (no CPU fallback)")
         acc = torch.zeros(tuple(patterns.shape[1:]), dtype=torch.float64, device=self.device)
         staging = self._stream_batches(patterns, items, batch_size, self.device,
-                                       lambda raw: accumulate_patterns(raw, acc))
+                                       lambda i, raw: accumulate_patterns(raw, acc))
         total = acc.cpu().numpy()    # the host's one wait: every batch has been added
         del staging
         return (total / patterns.shape[0]).astype(np.float32)

@@ -104,6 +104,8 @@ def test_correct_patterns_rejects_before_any_device_use(no_device):
         correct_patterns(np.zeros((1, 300, 300), np.uint8), (288, 288), PatternCorrection())
     with pytest.raises(ValueError, match="out must be"):
         correct_patterns(raw, (64, 64), PatternCorrection(), out=torch.empty(2, 1, 64, 60))
+    with pytest.raises(ValueError, match="out must be"):       # the plain ingest checks it too
+        D.ingest_patterns(raw, (64, 64), out=torch.empty(2, 1, 64, 60))
     with pytest.raises(TypeError, match="uint8, float32 or float64"):
         correct_patterns(raw.astype(np.int16), (64, 64), PatternCorrection())
     with pytest.raises(TypeError, match="PatternCorrection"):
