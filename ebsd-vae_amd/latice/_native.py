@@ -112,6 +112,10 @@ SIGNATURES = {
     "ebsdvae_accumulate_patterns": [P, I, I, I, I, P, P],
     "ebsdvae_resample_patterns": [P, I, I, I, I, I, I, I, I, I, I, P, P, I, P, P, I, F, P, P],
     "ebsdvae_average_neighbours": [P, I64, I, I, I64, I64, P, I, I, I, I, P, P],
+    "ebsdvae_nlpar_work": [I, I, I64, I, I, I, I],
+    "ebsdvae_nlpar_weights": [P, I64, I, I, I64, I64, I, I, I, I, ctypes.c_double, I,
+                              ctypes.c_double, ctypes.c_double, I, ctypes.c_double, P, P, P, P],
+    "ebsdvae_nlpar_average": [P, I64, I, I, I64, I64, P, I, I, I, I, P, P],
     "ebsdvae_index_latents_work": [I64, I, I, I],
     "ebsdvae_index_latents": [P, I64, P, P, I, I, I, ctypes.c_double, I, I, P, P, P, P, P, P, P, P, P],
 }
@@ -120,11 +124,12 @@ _RESTYPE = {"ebsdvae_last_error": ctypes.c_char_p, "ebsdvae_wgrad_reduce_work": 
             "ebsdvae_cosine_topk_work": ctypes.c_size_t,
             "ebsdvae_index_latents_work": ctypes.c_size_t,
             "ebsdvae_correct_patterns_work": ctypes.c_size_t,
+            "ebsdvae_nlpar_work": ctypes.c_size_t,
             "ebsdvae_heads_wgrad_work": ctypes.c_size_t, "ebsdvae_heads_work": ctypes.c_size_t, "ebsdvae_pack_split_bytes": ctypes.c_size_t}
 # queries that return a value rather than a status
 QUERIES = {"ebsdvae_version", "ebsdvae_conv_first_stat_tiles", "ebsdvae_conv3x3_stat_tiles", "ebsdvae_conv3x3_wgrad_slices",
            "ebsdvae_wgrad_reduce_batch_work", "ebsdvae_cosine_topk_work",
-           "ebsdvae_index_latents_work", "ebsdvae_correct_patterns_work",
+           "ebsdvae_index_latents_work", "ebsdvae_correct_patterns_work", "ebsdvae_nlpar_work",
            "ebsdvae_in_bwd_tiles", "ebsdvae_in_bwd_apply_tiles", "ebsdvae_in_bwd_final_tiles", "ebsdvae_wgrad_reduce_work", "ebsdvae_heads_wgrad_work", "ebsdvae_heads_work",
            "ebsdvae_conv3x3_split_supported", "ebsdvae_conv3x3_split_stat_tiles",
            "ebsdvae_conv3x3_split_pool_ok", "ebsdvae_conv3x3_fwd_split_first_ok",

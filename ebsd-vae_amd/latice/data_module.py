@@ -41,11 +41,11 @@ import torch
 from torch.utils.data import random_split
 
 from .patterns import (MAX_CORRECTED_SIDE, MAX_NEIGHBOUR_SIDE, MAX_RESAMPLE_FACTOR,  # noqa: F401
-                       MAX_RESAMPLED_SIDE, DetectorResample, NeighbourAverage, PatternCorrection,
-                       ScanIngest, _crop_offset, accumulate_patterns, average_neighbour_patterns,
+                       MAX_RESAMPLED_SIDE, NLPAR, DetectorResample, NeighbourAverage,
+                       PatternCorrection, ScanIngest, _crop_offset, accumulate_patterns, average_neighbour_patterns,
                        average_neighbour_range, check_resampled_correction, correct_patterns,
                        gaussian_taps, ingest_patterns, ingest_patterns_u8, neighbour_window,
-                       resample_axis, resample_denominator, resample_patterns)
+                       nlpar_patterns, nlpar_range, nlpar_weights, resample_axis, resample_denominator, resample_patterns)
 
 try:  # pragma: no cover - depends on the environment
     import pytorch_lightning as pl

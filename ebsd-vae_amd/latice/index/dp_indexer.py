@@ -24,6 +24,8 @@ path: same `IndexerConfig` and `DiffractionPatternIndexer` API and call contract
   runs through.  `neighbour_average=NeighbourAverage(...)` averages every transformed pattern
   with its neighbours on the scan grid between ingest and encoder; a host scan then streams
   through a device ring of transformed patterns (latice/index/scan.py `neighbour_schedule`).
+  `nlpar=NLPAR(...)` takes the averaging's place with weights from the pattern distances
+  (csrc/nlpar.hip): the same ring and schedule, one scan row and column further each way.
   `scan_background` streams a scan into its mean pattern, the usual static background.
 """
 from __future__ import annotations
@@ -44,8 +46,8 @@ from latice.index.faiss_db import (MAX_K, FaissLatentVectorDatabase,
 from latice.index.scan import (SCAN_F32, SCAN_F64, SCAN_U8, ScanIndexResult, neighbour_schedule,
                                open_scan, scan_batches, scan_dtype_code)
 from latice.model import VariationalAutoEncoder
-from latice.patterns import (DetectorResample, NeighbourAverage, PatternCorrection, ScanIngest,
-                             accumulate_patterns, average_neighbour_range)
+from latice.patterns import (NLPAR, DetectorResample, NeighbourAverage, PatternCorrection,
+                             ScanIngest, accumulate_patterns, average_neighbour_range, nlpar_range)
 
 logger = logging.getLogger(__name__)
 
@@ -225,7 +227,8 @@ class DiffractionPatternIndexer:
                    return_candidates: bool = False,
                    correction: PatternCorrection | None = None,
                    neighbour_average: NeighbourAverage | None = None,
-                   resample: DetectorResample | None = None) -> ScanIndexResult:
+                   resample: DetectorResample | None = None,
+                   nlpar: NLPAR | None = None) -> ScanIndexResult:
         """A whole scan in, an orientation map out, everything between on the device.
 
         `patterns` is a path to a .npy file (memory-mapped), a numpy array / memmap
@@ -256,8 +259,19 @@ class DiffractionPatternIndexer:
         intermediate and the plain ingest at equal size, and with a `correction` through that
         intermediate into `correct_patterns`, whose static background stays at detector shape
         and whose `dynamic_sigma` is in output pixels.  The intermediate is allocated once per
-        scan.  A device tensor is already transformed and cannot take one."""
+        scan.  A device tensor is already transformed and cannot take one.
+
+        With `nlpar` (an `NLPAR` whose scan_shape holds the N patterns) non-local pattern
+        averaging takes the place of `neighbour_average` (one or the other): ingest, correction
+        or resample, then NLPAR, then encoder.  A device tensor may take it; a host scan streams
+        through the same ring, which holds batch_size + 2 ((hr + 1) cols + hc + 1) patterns,
+        because a neighbour's noise estimate needs that neighbour's own surroundings.  The
+        result does not depend on batch_size."""
         _check_raw_stage("resample", resample, DetectorResample, patterns)
+        if nlpar is not None and not isinstance(nlpar, NLPAR):
+            raise TypeError(f"nlpar must be an NLPAR, got {type(nlpar).__name__}")
+        if nlpar is not None and neighbour_average is not None:
+            raise ValueError("index_scan takes `nlpar` or `neighbour_average`, not both")
         if neighbour_average is not None and not isinstance(neighbour_average, NeighbourAverage):
             raise TypeError("neighbour_average must be a NeighbourAverage, got "
                             f"{type(neighbour_average).__name__}")
@@ -289,8 +303,16 @@ class DiffractionPatternIndexer:
             n, dev = patterns.shape[0], self.device
             plan = ScanIngest(patterns.shape[1:], scan_dtype_code(patterns.dtype),
                               self.config.image_size, dev, min(batch_size, n), correction, resample)
-        if neighbour_average is not None:
-            neighbour_average.check(n)
+        # the averaging stage, if any: the record, its ring function and the window's half
+        # widths as the schedule sees them (NLPAR reads one row and column further)
+        stage, stage_range, stage_half = neighbour_average, average_neighbour_range, None
+        if nlpar is not None:
+            stage, stage_range = nlpar, nlpar_range
+            stage_half = (nlpar.half[0] + 1, nlpar.half[1] + 1)
+        elif neighbour_average is not None:
+            stage_half = neighbour_average.half
+        if stage is not None:
+            stage.check(n)
         k = min(top_n, self.db.get_count()) if return_candidates else 0
         buf, layout, res = _result_buffer(n, k, return_candidates, dev)
 
@@ -301,11 +323,11 @@ class DiffractionPatternIndexer:
         def average_index(ring, x, chunks):
             """Every chunk [a, b) averaged out of `ring` into x[:b - a], encoded and indexed."""
             for a, b in chunks:
-                average_neighbour_range(ring, neighbour_average, a, b - a, x)
+                stage_range(ring, stage, a, b - a, x)
                 encode_index(x[:b - a], a, b)
 
         staging = None
-        if on_device and neighbour_average is not None and n:
+        if on_device and stage is not None and n:
             ring = patterns.contiguous()     # a resident scan is its own ring
             with torch.cuda.device(dev):
                 x = torch.empty((min(batch_size, n),) + tuple(ring.shape[1:]),
@@ -316,9 +338,9 @@ class DiffractionPatternIndexer:
             for s in range(0, n, batch_size):
                 e = min(s + batch_size, n)
                 encode_index(patterns[s:e], s, e)
-        elif n and neighbour_average is not None:
+        elif n and stage is not None:
             staging = self._stream_scan_averaged(patterns, items, batch_size, dev, plan,
-                                                 neighbour_average, average_index)
+                                                 stage.scan_shape[1], stage_half, average_index)
         elif n:
             staging = self._stream_scan(patterns, items, batch_size, dev, plan, encode_index)
 
@@ -337,9 +359,10 @@ class DiffractionPatternIndexer:
                                     lambda i, raw: plan.plan(raw, x[:raw.shape[0]]),
                                     lambda i, s, e: encode_index(x[:e - s], s, e)) + (x,)
 
-    def _stream_scan_averaged(self, patterns, items, batch_size, dev, plan, neighbour_average,
+    def _stream_scan_averaged(self, patterns, items, batch_size, dev, plan, cols, half,
                               average_index):
-        """index_scan over a host scan with neighbour averaging: every staged batch is ingested,
+        """index_scan over a host scan of `cols` columns with neighbour averaging or NLPAR over
+        a reach of `half` = (rows, columns) each way: every staged batch is ingested,
         once, into its slots of a ring of transformed patterns (`neighbour_schedule`, one step
         per batch; in two parts where it passes the ring's end); the outputs that are complete
         after it are averaged from the ring into the encoder's batch buffer, chunk by chunk,
@@ -348,8 +371,7 @@ class DiffractionPatternIndexer:
         reads the old patterns."""
         h, w = self.config.image_size
         n = patterns.shape[0]
-        hr, hc = neighbour_average.half
-        schedule = neighbour_schedule(n, neighbour_average.scan_shape[1], hr, hc, batch_size)
+        schedule = neighbour_schedule(n, cols, half[0], half[1], batch_size)
         steps = schedule.steps
         with torch.cuda.device(dev):
             ring = torch.empty(schedule.ring_cap, 1, h, w, dtype=torch.float32, device=dev)

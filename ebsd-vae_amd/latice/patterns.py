@@ -10,6 +10,9 @@ in the reference, whose one transform (`DPdataset.__getitem__`) `latice.data_mod
                                            (csrc/resample.hip), in front of either ingest
     average_neighbour_patterns / _range    averaging over the scan grid (NeighbourAverage,
                                            csrc/neighbour.hip), between ingest and encoder
+    nlpar_patterns / _weights / _range     non-local pattern averaging: the same window with
+                                           weights from the pattern distances (NLPAR,
+                                           csrc/nlpar.hip), in the averaging's place
     ScanIngest                             the per-scan plan `index_scan` runs every staged
                                            batch through: checks, route and intermediate once
 
@@ -617,3 +620,160 @@ def average_neighbour_patterns(x: torch.Tensor, neighbour_average: NeighbourAver
     elif out.shape != x.shape:
         raise ValueError(f"out must be a {tuple(x.shape)} tensor, got {tuple(out.shape)}")
     return average_neighbour_range(x.contiguous(), neighbour_average, 0, x.shape[0], out)
+
+
+# ---------------------------------------------------------------- non-local pattern averaging
+def _positive(name: str, value) -> float:
+    v = float(value)
+    if not (v > 0.0 and math.isfinite(v)):
+        raise ValueError(f"{name} must be a positive finite number, got {value}")
+    return v
+
+
+@dataclass(frozen=True, eq=False)
+class NLPAR:
+    """Non-local pattern averaging and re-weighting (Brewick, Wright and Rowenhorst,
+    Ultramicroscopy 200, 2019), applied by `nlpar_patterns` and `index_scan(nlpar=...)`: every
+    transformed pattern of the `scan_shape` = (rows, cols) grid becomes the weighted mean of the
+    on-grid patterns of its `window_shape` window (odd sides of at most 5), each weighted by
+    exp(-d / lam^2), d = max((D - n v) / (v sqrt(2 n)), 0), with D the squared distance of the
+    two patterns over their n pixels and v the sum of their noise variances.  A variance is
+    `sigma`^2, or with `sigma=None` estimated per pattern from its nearest of the 8 surrounding
+    patterns, min D / (2 n), and not below `sigma_floor`^2.  With `dthresh` a neighbour whose
+    d exceeds it is dropped.  The centre weight is 1; the result is not rescaled."""
+
+    scan_shape: tuple
+    window_shape: tuple = (3, 3)
+    lam: float = 0.7
+    sigma: float | None = None
+    sigma_floor: float = 1e-3
+    dthresh: float | None = None
+
+    def __post_init__(self):
+        try:
+            rows, cols = (int(v) for v in self.scan_shape)
+        except (TypeError, ValueError):
+            raise ValueError(f"scan_shape must be (rows, cols), got {self.scan_shape!r}") from None
+        if rows < 1 or cols < 1 or rows * cols >= 1 << 31:
+            raise ValueError(f"scan_shape {self.scan_shape!r}: rows and cols must be positive "
+                             "(and rows * cols below 2^31)")
+        object.__setattr__(self, "scan_shape", (rows, cols))
+        try:
+            ny, nx = (int(v) for v in self.window_shape)
+        except (TypeError, ValueError):
+            raise ValueError(f"window_shape must be two integers, got {self.window_shape!r}") from None
+        for v in (ny, nx):
+            if not (1 <= v <= MAX_NEIGHBOUR_SIDE and v % 2 == 1):
+                raise ValueError(f"window_shape {self.window_shape!r}: sides must be odd and at most "
+                                 f"{MAX_NEIGHBOUR_SIDE}")
+        object.__setattr__(self, "window_shape", (ny, nx))
+        object.__setattr__(self, "lam", _positive("lam", self.lam))
+        object.__setattr__(self, "sigma_floor", _positive("sigma_floor", self.sigma_floor))
+        if self.sigma is not None:
+            object.__setattr__(self, "sigma", _positive("sigma", self.sigma))
+        if self.dthresh is not None:
+            dthresh = float(self.dthresh)
+            if not (dthresh >= 0.0 and math.isfinite(dthresh)):
+                raise ValueError(f"dthresh must be a non-negative finite number, got {self.dthresh}")
+            object.__setattr__(self, "dthresh", dthresh)
+
+    @property
+    def half(self) -> tuple[int, int]:
+        """(hr, hc): the window reaches hr scan rows and hc scan columns each way."""
+        return self.window_shape[0] // 2, self.window_shape[1] // 2
+
+    @property
+    def reach(self) -> int:
+        """(hr + 1) * cols + (hc + 1): how far, in flat scan index, the patterns lie that a
+        pattern's weights depend on (a neighbour's variance needs that neighbour's own ring)."""
+        hr, hc = self.half
+        return (hr + 1) * self.scan_shape[1] + (hc + 1)
+
+    def check(self, n: int) -> None:
+        rows, cols = self.scan_shape
+        if int(n) != rows * cols:
+            raise ValueError(f"the scan has {n} patterns, scan_shape {self.scan_shape} needs "
+                             f"{rows * cols}")
+
+
+def _nlpar_ring(ring: torch.Tensor, nlpar, who: str):
+    if not isinstance(nlpar, NLPAR):
+        raise TypeError(f"nlpar must be an NLPAR, got {type(nlpar).__name__}")
+    if not (torch.is_tensor(ring) and ring.is_cuda):
+        raise RuntimeError(f"{who} needs a tensor on a ROCm device (no CPU fallback)")
+    if not (ring.dtype == torch.float32 and ring.dim() == 4 and ring.shape[1] == 1
+            and ring.is_contiguous()):
+        raise ValueError(f"{who}: patterns must be a contiguous (N, 1, h, w) float32 tensor, got "
+                         f"{tuple(ring.shape)} {ring.dtype}")
+
+
+def _nlpar_weights_range(ring: torch.Tensor, nlpar: NLPAR, p0: int, count: int):
+    """(weights (count, 2 hr + 1, 2 hc + 1), sigma (count,)) of the outputs [p0, p0 + count)
+    out of a ring (`ebsdvae_nlpar_weights`); the scratch is stream-ordered and freed on return."""
+    cap, _, h, w = ring.shape
+    (hr, hc), (rows, cols) = nlpar.half, nlpar.scan_shape
+    nbytes = N.call("ebsdvae_nlpar_work", rows, cols, int(count), hr, hc, h, w)
+    if not nbytes:
+        raise ValueError(f"nlpar: {count} outputs of ({h}, {w}) patterns on a {rows} x {cols} grid "
+                         "are refused (h * w must be a multiple of 4 below 2^24)")
+    with torch.cuda.device(ring.device):
+        work = torch.empty(nbytes, dtype=torch.uint8, device=ring.device)
+        weights = torch.empty(count, 2 * hr + 1, 2 * hc + 1, dtype=torch.float32, device=ring.device)
+        sigma = torch.empty(count, dtype=torch.float32, device=ring.device)
+    N.call("ebsdvae_nlpar_weights", N.ptr(ring), cap, rows, cols, int(p0), int(count), hr, hc, h, w,
+           nlpar.lam, int(nlpar.sigma is not None), nlpar.sigma or 0.0, nlpar.sigma_floor,
+           int(nlpar.dthresh is not None), nlpar.dthresh or 0.0, N.ptr(weights), N.ptr(sigma),
+           work.data_ptr(), N.stream(ring.device))
+    return weights, sigma
+
+
+def nlpar_range(ring: torch.Tensor, nlpar: NLPAR, p0: int, count: int,
+                out: torch.Tensor) -> torch.Tensor:
+    """out[:count] = the NLPAR-averaged patterns [p0, p0 + count) of the scan (csrc/nlpar.hip).
+    `ring` (cap, 1, h, w) float32 holds scan pattern q in slot q % cap, and every on-grid pattern
+    within `nlpar.reach` of the range is resident; a resident scan is its own ring (cap = N).
+    `out` is contiguous, holds at least `count` patterns and does not overlap `ring`."""
+    _nlpar_ring(ring, nlpar, "nlpar_range")
+    cap, _, h, w = ring.shape
+    if not (out.is_cuda and out.is_contiguous() and out.dtype == torch.float32
+            and out.numel() >= count * h * w):
+        raise ValueError(f"out must be a contiguous float32 device tensor of at least {count} "
+                         f"({h}, {w}) patterns, got {tuple(out.shape)}")
+    if count == 0:
+        return out
+    weights, _ = _nlpar_weights_range(ring, nlpar, p0, count)
+    (hr, hc), (rows, cols) = nlpar.half, nlpar.scan_shape
+    N.call("ebsdvae_nlpar_average", N.ptr(ring), cap, rows, cols, int(p0), int(count),
+           N.ptr(weights), hr, hc, h, w, N.ptr(out), N.stream(ring.device))
+    return out
+
+
+def _nlpar_scan(x, nlpar, who: str) -> torch.Tensor:
+    if not isinstance(nlpar, NLPAR):
+        raise TypeError(f"nlpar must be an NLPAR, got {type(nlpar).__name__}")
+    if not torch.is_tensor(x) or not x.is_cuda:
+        raise RuntimeError(f"{who} needs a tensor on a ROCm device (no CPU fallback)")
+    if x.dim() != 4 or x.shape[1] != 1 or x.dtype != torch.float32:
+        raise ValueError(f"patterns must be (N, 1, h, w) float32, got {tuple(x.shape)} {x.dtype}")
+    nlpar.check(x.shape[0])
+    return x.contiguous()
+
+
+def nlpar_weights(x: torch.Tensor, nlpar: NLPAR):
+    """The weights NLPAR gives a resident scan x (N, 1, h, w): (weights (N, 2 hr + 1, 2 hc + 1),
+    sigma (N,)) as float32 device tensors.  weights[p] is the window of pattern p before the
+    normalisation, centre 1: 1 / weights[p].sum() is the share that stays on the pattern itself,
+    what one looks at to choose `lam`."""
+    x = _nlpar_scan(x, nlpar, "nlpar_weights")
+    return _nlpar_weights_range(x, nlpar, 0, x.shape[0])
+
+
+def nlpar_patterns(x: torch.Tensor, nlpar: NLPAR, out: torch.Tensor | None = None) -> torch.Tensor:
+    """A resident scan of transformed patterns x (N, 1, h, w) float32 on the device -> a new
+    tensor of that shape (or `out`) in which every pattern is the NLPAR mean of its window."""
+    x = _nlpar_scan(x, nlpar, "nlpar_patterns")
+    if out is None:
+        out = torch.empty_like(x, memory_format=torch.contiguous_format)
+    elif out.shape != x.shape:
+        raise ValueError(f"out must be a {tuple(x.shape)} tensor, got {tuple(out.shape)}")
+    return nlpar_range(x, nlpar, 0, x.shape[0], out)

@@ -627,6 +627,42 @@ int ebsdvae_average_neighbours(const float* src, long long ring_cap, int rows, i
                                long long p0, long long count, const float* weights, int hr,
                                int hc, int h, int w, float* dst, ebsdvae_stream_t stream);
 
+/* ---- non-local pattern averaging, NLPAR ("Non-local pattern averaging")
+ * The neighbour averaging above with weights that follow the patterns.  T, the grid and the ring
+ * are as there; n = h w, D(p, q) = sum over pixels of (T[p] - T[q])^2.  Per pattern
+ *   s_p = max(min D(p, q) / (2 n), sigma_floor^2), q over the on-grid patterns of the 3 x 3 ring
+ *         around p whatever the window (s_p = sigma_floor^2 where there is none); with
+ *         fixed_sigma != 0, s_p = sigma^2 for every p;
+ * and per window offset (a, b) != (0, 0) with q = (i + a, j + b) on the grid
+ *   v = s_p + s_q,  d = max((D(p, q) - n v) / (v sqrt(2 n)), 0),  Wt[p][a][b] = exp(-d / lam^2),
+ *   0 where cut != 0 and d > dthresh.  The centre weight is 1, a weight off the grid 0.
+ * D is summed in a fixed order (float32 partials per block of 1024 pixels, added in double,
+ * rounded to float32 once); what follows it is float32.  No atomics: weights, sigma and the
+ * averaged patterns are functions of T, the grid and the parameters alone, bit for bit, not of
+ * p0, count or ring_cap.
+ * ebsdvae_nlpar_weights: for p in [p0, p0 + count) writes weights (count, 2 hr + 1, 2 hc + 1)
+ * and, unless NULL, sigma_out (count,) = sqrt(s_p).  It reads patterns within (hr + 1) cols +
+ * (hc + 1) of the range (a neighbour's s_q needs that neighbour's own ring): every on-grid
+ * pattern of the flat range [p0 - that, p0 + count + that) is resident in src.  work: device
+ * scratch of ebsdvae_nlpar_work(rows, cols, count, hr, hc, h, w) bytes, which answers 0 for the
+ * shapes the call refuses (half widths outside 0..2, a grid that is not positive or holds 2^31
+ * patterns, h * w % 4 != 0 or h * w >= 2^24, count outside 0..rows * cols).
+ * Nonzero, and nothing written, for those, a null src, weights or work, lam, sigma_floor or
+ * (with fixed_sigma) sigma not positive and finite, (with cut) a negative dthresh, a range that
+ * leaves the grid, or ring_cap < min(rows * cols, count + 2 ((hr + 1) cols + (hc + 1))).
+ * ebsdvae_nlpar_average: dst[p - p0] = sum Wt[p][a][b] T[q] / sum Wt[p][a][b] with the weights
+ * of ebsdvae_nlpar_weights for the same range: the float32 fma chains and the one division of
+ * ebsdvae_average_neighbours, its ring bound (count + 2 (hr cols + hc)) and its refusals. */
+size_t ebsdvae_nlpar_work(int rows, int cols, long long count, int hr, int hc, int h, int w);
+int ebsdvae_nlpar_weights(const float* src, long long ring_cap, int rows, int cols, long long p0,
+                          long long count, int hr, int hc, int h, int w, double lam,
+                          int fixed_sigma, double sigma, double sigma_floor, int cut,
+                          double dthresh, float* weights, float* sigma_out, void* work,
+                          ebsdvae_stream_t stream);
+int ebsdvae_nlpar_average(const float* src, long long ring_cap, int rows, int cols, long long p0,
+                          long long count, const float* weights, int hr, int hc, int h, int w,
+                          float* dst, ebsdvae_stream_t stream);
+
 /* ---- whole-scan indexing: search + consensus in one call ------------------------------
  * ebsdvae_cosine_topk followed by ebsdvae_orient_consensus without the launch boundary
  * between them: the wave that merges a query's top-k list (candidate l in lane l) loads
