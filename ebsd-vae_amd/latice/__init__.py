@@ -6,7 +6,10 @@ Modules this package replaces (same names, classes and call contracts as the ref
 `latice._native`.  `latice.patterns` holds the device pattern stages the reference does not
 have (batched ingest, background correction, detector binning, neighbour averaging).
 
-Modules it does not replace -- `latice.utils` (plotting, IPF colour keys), the Chroma vector
+`latice.index.maps` builds the scan maps of an indexed scan on the device, the reference's IPF
+colours (`latice.utils.utils.get_color_key`) among them.
+
+Modules it does not replace -- `latice.utils` (plotting, the per-orientation colour key), the Chroma vector
 database `latice.index.chroma_db`, the legacy `latice.index.latent_embedding` -- are taken
 from a reference checkout when `LATICE_REFERENCE_ROOT` names one (the directory holding the
 reference's `latice/` package): its package directories are appended to `__path__`, so this

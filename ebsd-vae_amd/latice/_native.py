@@ -118,6 +118,9 @@ SIGNATURES = {
     "ebsdvae_nlpar_average": [P, I64, I, I, I64, I64, P, I, I, I, I, P, P],
     "ebsdvae_index_latents_work": [I64, I, I, I],
     "ebsdvae_index_latents": [P, I64, P, P, I, I, I, ctypes.c_double, I, I, P, P, P, P, P, P, P, P, P],
+    "ebsdvae_ipf_colors": [P, I64, I, P, P],
+    "ebsdvae_orientation_similarity": [P, I, I, I, I, I, P, P],
+    "ebsdvae_kernel_misorientation": [P, I, I, I, ctypes.c_double, P, P],
 }
 _RESTYPE = {"ebsdvae_last_error": ctypes.c_char_p, "ebsdvae_wgrad_reduce_work": ctypes.c_size_t,
             "ebsdvae_wgrad_reduce_batch_work": ctypes.c_size_t,
@@ -137,7 +140,7 @@ QUERIES = {"ebsdvae_version", "ebsdvae_conv_first_stat_tiles", "ebsdvae_conv3x3_
            "ebsdvae_conv3x3_dwgrad_slices", "ebsdvae_conv3x3_dwgrad_stat_tiles"}
 
 # include/ebsdvae.h EBSDVAE_ABI_VERSION: the signatures above
-ABI_VERSION = 2
+ABI_VERSION = 3
 
 _lib = None
 _lock = threading.Lock()

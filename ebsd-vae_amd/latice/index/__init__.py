@@ -6,7 +6,15 @@ with the dictionary resident in HBM: exact cosine top-k and the orientation cons
 HIP kernels (csrc/search.hip, csrc/orient.hip; fused for whole scans in csrc/scan_index.hip,
 `DiffractionPatternIndexer.index_scan`).  Other reference modules of this package
 (chroma_db, latent_embedding) resolve from LATICE_REFERENCE_ROOT (see latice/__init__.py).
+`maps` holds the scan maps built from an indexed scan's result rows (csrc/scan_maps.hip): IPF
+colours, the orientation similarity map and the kernel average misorientation.
 """
 from latice import _extend_path
 
 _extend_path(__path__, "index")
+
+from latice.index.maps import (ScanMaps, ipf_colors, kernel_average_misorientation,  # noqa: E402
+                               orientation_similarity_map)
+
+__all__ = ["ScanMaps", "ipf_colors", "kernel_average_misorientation",
+           "orientation_similarity_map"]

@@ -27,6 +27,9 @@ path: same `IndexerConfig` and `DiffractionPatternIndexer` API and call contract
   `nlpar=NLPAR(...)` takes the averaging's place with weights from the pattern distances
   (csrc/nlpar.hip): the same ring and schedule, one scan row and column further each way.
   `scan_background` streams a scan into its mean pattern, the usual static background.
+  `maps=ScanMaps(...)` appends the scan maps (latice/index/maps.py, csrc/scan_maps.hip: IPF
+  colours, orientation similarity, kernel average misorientation), built from the result rows
+  behind the last batch, to the same result buffer and the same single copy back.
 """
 from __future__ import annotations
 
@@ -43,6 +46,8 @@ from latice.data_module import DPDataModule, PatternTransform, create_default_tr
 from latice.index.faiss_db import (MAX_K, FaissLatentVectorDatabase,
                                    FaissLatentVectorDatabaseConfig, LatentIndexResult,
                                    OrientationResult)
+from latice.index.maps import (IPF_DIRECTIONS, ScanMaps, ipf_rows, misorientation_rows,
+                               similarity_rows)
 from latice.index.scan import (SCAN_F32, SCAN_F64, SCAN_U8, ScanIndexResult, neighbour_schedule,
                                open_scan, scan_batches, scan_dtype_code)
 from latice.model import VariationalAutoEncoder
@@ -87,7 +92,7 @@ def _default_db(dimension: int, device: torch.device):
 
 
 _NUMPY = {torch.float64: np.float64, torch.int64: np.int64, torch.float32: np.float32,
-          torch.int32: np.int32}
+          torch.int32: np.int32, torch.uint8: np.uint8}
 
 
 def _check_raw_stage(name: str, stage, cls, patterns) -> None:
@@ -102,34 +107,64 @@ def _check_raw_stage(name: str, stage, cls, patterns) -> None:
                          "host scans of raw detector patterns")
 
 
-def _result_buffer(n: int, k: int, candidates: bool, dev):
+def _result_buffer(n: int, k: int, candidates: bool, dev, maps: ScanMaps | None = None):
     """The results of an n-pattern scan (k candidates per pattern if `candidates`) as views
-    of ONE device buffer, so one copy brings them all back.  Returns (the buffer, its layout
-    [(name, dtype, shape, byte offset, bytes)], the views as a `LatentIndexResult`)."""
-    # the 8-byte fields come first to keep every view aligned
+    of ONE device buffer, so one copy brings them all back; with `maps`, the scan maps are
+    further fields of it.  Returns (the buffer, its layout [(name, dtype, shape, byte offset,
+    bytes)], the index fields as a `LatentIndexResult`, the map fields by name)."""
+    # the 8-byte fields come first to keep every view aligned, the bytes last
     fields = [("best", torch.float64, (n, 3)), ("row", torch.int64, (n,))]
     fields += [("cand_idx", torch.int64, (n, k))] if candidates else []
     fields += [("score", torch.float32, (n,)), ("success", torch.int32, (n,)),
                ("n_similar", torch.int32, (n,))]
     fields += [("cand_scores", torch.float32, (n, k))] if candidates else []
+    map_fields = []
+    if maps is not None:
+        map_fields += [("osm", torch.float32, (n,))] if maps.similarity else []
+        map_fields += [("kam", torch.float32, (n,))] if maps.kam else []
+        map_fields += [("ipf_" + d, torch.uint8, (n, 3)) for d in maps.ipf]
     layout, end = [], 0
-    for name, dt, shape in fields:
+    for name, dt, shape in fields + map_fields:
         nbytes = int(np.prod(shape)) * torch.empty((), dtype=dt).element_size()
         layout.append((name, dt, shape, end, nbytes))
         end += nbytes
     buf = torch.empty(max(end, 8), dtype=torch.uint8, device=dev)
-    return buf, layout, LatentIndexResult(**{name: buf[o:o + nb].view(dt).view(shape)
-                                             for name, dt, shape, o, nb in layout})
+    views = {name: buf[o:o + nb].view(dt).view(shape) for name, dt, shape, o, nb in layout}
+    map_views = {name: views.pop(name) for name, _, _ in map_fields}
+    return buf, layout, LatentIndexResult(**views), map_views
 
 
-def _unpack_result(buf: torch.Tensor, layout) -> ScanIndexResult:
+def _unpack_result(buf: torch.Tensor, layout, maps: ScanMaps | None = None) -> ScanIndexResult:
     """The one device-to-host copy of a scan's results (and the host's only wait)."""
     host = buf.cpu().numpy()
     h = {name: host[o:o + nb].view(_NUMPY[dt]).reshape(shape) for name, dt, shape, o, nb in layout}
-    return ScanIndexResult(orientations=h["best"], success=h["success"].astype(bool),
-                           scores=h["score"], top_index=h["row"], n_similar=h["n_similar"],
-                           candidate_indices=h.get("cand_idx"),
-                           candidate_scores=h.get("cand_scores"))
+    result = ScanIndexResult(orientations=h["best"], success=h["success"].astype(bool),
+                             scores=h["score"], top_index=h["row"], n_similar=h["n_similar"],
+                             candidate_indices=h.get("cand_idx"),
+                             candidate_scores=h.get("cand_scores"))
+    if maps is not None:
+        grid = maps.scan_shape
+        result.ipf_colors = {d: h["ipf_" + d].reshape(grid + (3,)) for d in maps.ipf}
+        if maps.similarity:
+            result.orientation_similarity = h["osm"].reshape(grid)
+        if maps.kam:
+            result.kam = h["kam"].reshape(grid)
+    return result
+
+
+def _run_maps(maps: ScanMaps, res: LatentIndexResult, views: dict) -> None:
+    """The scan maps of the whole scan's result rows `res` into their fields `views` of the result
+    buffer, on the current stream: behind the last batch, in front of the copy back."""
+    for d in maps.ipf:
+        ipf_rows(res.best, IPF_DIRECTIONS[d], views["ipf_" + d])
+        if maps.mask_failed:
+            views["ipf_" + d].masked_fill_((res.success == 0).unsqueeze(1), 0)
+    if maps.similarity:
+        similarity_rows(res.cand_idx, maps.scan_shape, maps.connectivity,
+                        maps.similarity_normalize, views["osm"])
+    if maps.kam:
+        misorientation_rows(res.best, maps.scan_shape, maps.connectivity, maps.kam_max_angle,
+                            views["kam"])
 
 
 class DiffractionPatternIndexer:
@@ -228,7 +263,8 @@ class DiffractionPatternIndexer:
                    correction: PatternCorrection | None = None,
                    neighbour_average: NeighbourAverage | None = None,
                    resample: DetectorResample | None = None,
-                   nlpar: NLPAR | None = None) -> ScanIndexResult:
+                   nlpar: NLPAR | None = None,
+                   maps: ScanMaps | None = None) -> ScanIndexResult:
         """A whole scan in, an orientation map out, everything between on the device.
 
         `patterns` is a path to a .npy file (memory-mapped), a numpy array / memmap
@@ -266,7 +302,17 @@ class DiffractionPatternIndexer:
         or resample, then NLPAR, then encoder.  A device tensor may take it; a host scan streams
         through the same ring, which holds batch_size + 2 ((hr + 1) cols + hc + 1) patterns,
         because a neighbour's noise estimate needs that neighbour's own surroundings.  The
-        result does not depend on batch_size."""
+        result does not depend on batch_size.
+
+        With `maps` (a `ScanMaps` whose scan_shape holds the N patterns, and equals the
+        scan_shape of `neighbour_average` / `nlpar` when one is given) the requested scan maps
+        -- IPF colours, orientation similarity, kernel average misorientation
+        (latice/index/maps.py) -- are built once on the compute stream from the result rows of
+        the whole scan, after the last batch is queued, for host and tensor scans alike.  They
+        are further fields of the one result buffer (still one copy back and one host wait) and
+        of the `ScanIndexResult`.  The similarity map needs every pattern's candidate rows on
+        the device: without `return_candidates` they live in a device tensor that is not copied
+        back.  Without `maps` nothing runs differently."""
         _check_raw_stage("resample", resample, DetectorResample, patterns)
         if nlpar is not None and not isinstance(nlpar, NLPAR):
             raise TypeError(f"nlpar must be an NLPAR, got {type(nlpar).__name__}")
@@ -313,8 +359,21 @@ class DiffractionPatternIndexer:
             stage_half = neighbour_average.half
         if stage is not None:
             stage.check(n)
-        k = min(top_n, self.db.get_count()) if return_candidates else 0
-        buf, layout, res = _result_buffer(n, k, return_candidates, dev)
+        if maps is not None:
+            if not isinstance(maps, ScanMaps):
+                raise TypeError(f"maps must be a ScanMaps, got {type(maps).__name__}")
+            maps.check(n)
+            if stage is not None and tuple(stage.scan_shape) != maps.scan_shape:
+                raise ValueError(f"maps.scan_shape {maps.scan_shape} differs from the scan_shape "
+                                 f"{tuple(stage.scan_shape)} of the averaging stage")
+        need_rows = maps is not None and maps.similarity
+        k = min(top_n, self.db.get_count()) if return_candidates or need_rows else 0
+        if need_rows and k < 1:
+            raise ValueError("the similarity map needs candidate rows: the dictionary is empty")
+        buf, layout, res, map_views = _result_buffer(n, k, return_candidates, dev, maps)
+        if need_rows and not return_candidates:
+            # the whole scan's candidate rows, for the similarity map alone: never copied back
+            res.cand_idx = torch.empty(n, k, dtype=torch.int64, device=dev)
 
         def encode_index(x, a, b):
             """Transformed patterns x of the scan's [a, b) -> their rows of the result."""
@@ -344,7 +403,10 @@ class DiffractionPatternIndexer:
         elif n:
             staging = self._stream_scan(patterns, items, batch_size, dev, plan, encode_index)
 
-        result = _unpack_result(buf, layout)     # the host's only wait
+        if maps is not None:
+            with torch.cuda.device(dev):
+                _run_maps(maps, res, map_views)
+        result = _unpack_result(buf, layout, maps)     # the host's only wait
         del staging                  # every copy-stream buffer outlived its last consumer
         return result
 

@@ -25,6 +25,10 @@ class ScanIndexResult:
     n_similar: np.ndarray               # (N,) int32: candidates within the threshold
     candidate_indices: np.ndarray | None = None   # (N, k) int64, best first
     candidate_scores: np.ndarray | None = None    # (N, k) float32
+    # the scan maps of `index_scan(maps=ScanMaps(...))` on its (rows, cols) grid (latice/index/maps.py)
+    ipf_colors: dict | None = None                # direction -> (rows, cols, 3) uint8
+    orientation_similarity: np.ndarray | None = None   # (rows, cols) float32
+    kam: np.ndarray | None = None                 # (rows, cols) float32, degrees
 
     def __len__(self) -> int:
         return int(self.success.shape[0])

@@ -38,8 +38,10 @@ typedef void* ebsdvae_stream_t; /* hipStream_t */
 const char* ebsdvae_last_error(void);
 /* ABI version of this header; ebsdvae_version() returns the library's.  Bumped on every
  * incompatible signature change (2: ebsdvae_heads_fwd / _bwd / ebsdvae_latent_mu take a
- * caller-owned `work` scratch pointer).  Callers must check it before the first call. */
-#define EBSDVAE_ABI_VERSION 2
+ * caller-owned `work` scratch pointer; 3: the scan maps, ebsdvae_ipf_colors /
+ * ebsdvae_orientation_similarity / ebsdvae_kernel_misorientation, which the binding requires).
+ * Callers must check it before the first call. */
+#define EBSDVAE_ABI_VERSION 3
 int ebsdvae_version(void);
 
 /* ---- stream ordering ------------------------------------------------------------------
@@ -681,6 +683,59 @@ int ebsdvae_index_latents(const float* db, long long N, const double* orientatio
                           float* top_score, long long* top_row, int* n_similar,
                           float* cand_scores, long long* cand_idx, void* work,
                           ebsdvae_stream_t stream);
+
+/* ---- scan maps ("Scan maps") -------------------------------------
+ * What a finished scan is looked at with, from the result rows of ebsdvae_index_latents.  The
+ * scan's rows * cols points lie on a grid in row-major order, point p at (i, j) = (p / cols,
+ * p % cols); its neighbours are the on-grid points (i + a, j + b), (a, b) != (0, 0), of the cross
+ * |a| + |b| = 1 (connectivity 4) or the square |a|, |b| <= 1 (connectivity 8), visited a ascending
+ * then b ascending.  All float arithmetic is float64 (scipy 1.15 `Rotation` conventions, QUAT_SYM
+ * of latice/utils/constants.py:13-39 in its order).  No scratch, no atomics: every output is a
+ * function of its inputs alone, bit for bit.
+ *
+ * ebsdvae_ipf_colors: rgb (n, 3) uint8 = the inverse-pole-figure colour of euler (n, 3), ZXZ
+ * degrees: get_color_key (latice/utils/utils.py:206-240) with mode ipf_x / ipf_y / ipf_z for
+ * axis 0 / 1 / 2.  Per orientation, ColorKeyGenerator.generate_ipf_color
+ * (latice/utils/colorkey.py:64-130) step by step:
+ *   v = row `axis` of from_euler("zxz", e, degrees=True).as_matrix(), divided by its norm;
+ *   e_t = M_t v for the 24 matrices M_t of QUAT_SYM in order, then -M_t v for the same 24;
+ *   each e_t with z < 0 is negated; chi = acos(z), eta = atan2(y, x);
+ *   the FIRST t with 0 <= eta <= 45 deg and 0 <= chi <= acos(1 / sqrt 3) wins, else the last tried
+ *     (the sector is larger than the fundamental triangle: about a fifth of all directions have
+ *     two distinct equivalents inside it, so the order is part of the result);
+ *   c = chi / acos(1 / sqrt 3) and f = |eta| / 45 deg, both formed in degrees as the reference
+ *     does; (r, g, b) = sqrt(1 - c, (1 - f) c, f c); level = round(255 x / max(r, g, b)), ties
+ *     to even.
+ * A z one ulp above 1 (the exact [001] pole) counts as 1.  A channel that is not a number is 0.
+ * A non-finite Euler row gives (0, 0, 0).  n = 0 is a successful no-op.
+ * Nonzero, and nothing written, for a null pointer, n < 0 or axis outside 0..2.
+ *
+ * ebsdvae_orientation_similarity: the orientation similarity map of dictionary indexing
+ * (Marquardt et al. 2017).  cand_idx (rows * cols, k) int64 are the top-k dictionary rows of every
+ * point (what ebsdvae_index_latents writes; entries < 0 are "none").  With c_q = the number of
+ * entries >= 0 of row p that also occur in row q,
+ *   osm[p] = float32(sum of c_q over the neighbours q) / float32(number of neighbours),
+ *   then / float32(k) if normalize != 0; 0 where p has no neighbour.
+ * The sum is an integer of at most 8 * 64, so the one or two float32 divisions are the only
+ * roundings.  Nonzero, and nothing written, for a null pointer, k outside 1..64, rows or cols
+ * < 1, rows * cols >= 2^31 or a connectivity other than 4 or 8.
+ *
+ * ebsdvae_kernel_misorientation: the kernel average misorientation of euler (rows * cols, 3), ZXZ
+ * degrees, under the cubic group.  Per neighbour q of p,
+ *   w = min over the 24 operators S of QUAT_SYM, in order, of |conj(q_p) (S q_q)| in degrees
+ * (the magnitude 2 atan2(|vector part|, |scalar part|): ebsdvae_orient_consensus' convention);
+ * the neighbours with w <= max_deg are kept (max_deg = +inf keeps all) and
+ *   kam[p] = float32(float64 sum of the kept w, in neighbour order / their number), 0 when none
+ * is kept.  kam[p] is NaN where p's own row is not finite; a neighbour whose row is not finite
+ * is skipped.  Nonzero, and nothing written, for a null pointer, rows or cols < 1,
+ * rows * cols >= 2^31, a connectivity other than 4 or 8, or a max_deg that is NaN or negative. */
+int ebsdvae_ipf_colors(const double* euler, long long n, int axis, unsigned char* rgb,
+                       ebsdvae_stream_t stream);
+int ebsdvae_orientation_similarity(const long long* cand_idx, int k, int rows, int cols,
+                                   int connectivity, int normalize, float* osm,
+                                   ebsdvae_stream_t stream);
+int ebsdvae_kernel_misorientation(const double* euler, int rows, int cols, int connectivity,
+                                  double max_deg, float* kam, ebsdvae_stream_t stream);
 
 #ifdef __cplusplus
 }
