@@ -349,14 +349,11 @@ class DiffractionPatternIndexer:
             n, dev = patterns.shape[0], self.device
             plan = ScanIngest(patterns.shape[1:], scan_dtype_code(patterns.dtype),
                               self.config.image_size, dev, min(batch_size, n), correction, resample)
-        # the averaging stage, if any: the record, its ring function and the window's half
-        # widths as the schedule sees them (NLPAR reads one row and column further)
-        stage, stage_range, stage_half = neighbour_average, average_neighbour_range, None
+        # the averaging stage, if any: the record and its ring function (the schedule plans
+        # with the record's schedule_half)
+        stage, stage_range = neighbour_average, average_neighbour_range
         if nlpar is not None:
             stage, stage_range = nlpar, nlpar_range
-            stage_half = (nlpar.half[0] + 1, nlpar.half[1] + 1)
-        elif neighbour_average is not None:
-            stage_half = neighbour_average.half
         if stage is not None:
             stage.check(n)
         if maps is not None:
@@ -399,7 +396,8 @@ class DiffractionPatternIndexer:
                 encode_index(patterns[s:e], s, e)
         elif n and stage is not None:
             staging = self._stream_scan_averaged(patterns, items, batch_size, dev, plan,
-                                                 stage.scan_shape[1], stage_half, average_index)
+                                                 stage.scan_shape[1], stage.schedule_half,
+                                                 average_index)
         elif n:
             staging = self._stream_scan(patterns, items, batch_size, dev, plan, encode_index)
 

@@ -481,6 +481,60 @@ MAX_NEIGHBOUR_SIDE = 5   # ebsdvae_average_neighbours' window limit per axis
 _WINDOWS = ("rectangular", "circular", "gaussian")
 
 
+def _grid_and_window(scan_shape=None, window_shape=None):
+    """(scan_shape, window_shape) as tuples of two ints, each checked where it is given: a grid
+    of positive sides with fewer than 2^31 patterns, a window of odd sides of at most 5."""
+    if scan_shape is not None:
+        try:
+            rows, cols = (int(v) for v in scan_shape)
+        except (TypeError, ValueError):
+            raise ValueError(f"scan_shape must be (rows, cols), got {scan_shape!r}") from None
+        if rows < 1 or cols < 1 or rows * cols >= 1 << 31:
+            raise ValueError(f"scan_shape {scan_shape!r}: rows and cols must be positive "
+                             "(and rows * cols below 2^31)")
+        scan_shape = (rows, cols)
+    if window_shape is not None:
+        try:
+            ny, nx = (int(v) for v in window_shape)
+        except (TypeError, ValueError):
+            raise ValueError(f"window_shape must be two integers, got {window_shape!r}") from None
+        for v in (ny, nx):
+            if not (1 <= v <= MAX_NEIGHBOUR_SIDE and v % 2 == 1):
+                raise ValueError(f"window_shape {window_shape!r}: sides must be odd and at most "
+                                 f"{MAX_NEIGHBOUR_SIDE}")
+        window_shape = (ny, nx)
+    return scan_shape, window_shape
+
+
+class _ScanStage:
+    """What the records of the two scan-grid averagings share: each has a `scan_shape` =
+    (rows, cols) and an odd-sided `window_shape`."""
+
+    @property
+    def half(self) -> tuple[int, int]:
+        """(hr, hc): the window reaches hr scan rows and hc scan columns each way."""
+        return self.window_shape[0] // 2, self.window_shape[1] // 2
+
+    @property
+    def schedule_half(self) -> tuple[int, int]:
+        """The half widths of everything an output depends on: what the streaming schedule of
+        `index_scan` keeps resident around a chunk."""
+        return self.half
+
+    @property
+    def reach(self) -> int:
+        """hr * cols + hc of `schedule_half`: how far, in flat scan index, the patterns lie that
+        an output depends on."""
+        hr, hc = self.schedule_half
+        return hr * self.scan_shape[1] + hc
+
+    def check(self, n: int) -> None:
+        rows, cols = self.scan_shape
+        if int(n) != rows * cols:
+            raise ValueError(f"the scan has {n} patterns, scan_shape {self.scan_shape} needs "
+                             f"{rows * cols}")
+
+
 def neighbour_window(window: str = "circular", window_shape=(3, 3), std: float = 1.0) -> np.ndarray:
     """A named averaging window of odd shape (2 hr + 1, 2 hc + 1), at most 5 x 5, built in
     float64 over the offsets (a, b) from the centre and rounded to float32: "rectangular" all
@@ -488,14 +542,7 @@ def neighbour_window(window: str = "circular", window_shape=(3, 3), std: float =
     exp(-(a^2 + b^2) / (2 std^2))."""
     if window not in _WINDOWS:
         raise ValueError(f"window must be one of {_WINDOWS}, got {window!r}")
-    try:
-        ny, nx = (int(v) for v in window_shape)
-    except (TypeError, ValueError):
-        raise ValueError(f"window_shape must be two integers, got {window_shape!r}") from None
-    for v in (ny, nx):
-        if not (1 <= v <= MAX_NEIGHBOUR_SIDE and v % 2 == 1):
-            raise ValueError(f"window_shape {window_shape!r}: sides must be odd and at most "
-                             f"{MAX_NEIGHBOUR_SIDE}")
+    _, (ny, nx) = _grid_and_window(window_shape=window_shape)
     std = float(std)
     if not (std > 0.0 and math.isfinite(std)):
         raise ValueError(f"std must be a positive finite number, got {std}")
@@ -512,7 +559,7 @@ def neighbour_window(window: str = "circular", window_shape=(3, 3), std: float =
 
 
 @dataclass(frozen=True, eq=False)
-class NeighbourAverage:
+class NeighbourAverage(_ScanStage):
     """Averaging of every transformed pattern with its neighbours on the scan grid
     (kikuchipy's `average_neighbour_patterns`), applied by `average_neighbour_patterns` and
     `index_scan(neighbour_average=...)`.  The scan's N = rows * cols patterns lie on the grid
@@ -530,14 +577,7 @@ class NeighbourAverage:
     _device_state: dict = field(default_factory=dict, init=False, repr=False)
 
     def __post_init__(self):
-        try:
-            rows, cols = (int(v) for v in self.scan_shape)
-        except (TypeError, ValueError):
-            raise ValueError(f"scan_shape must be (rows, cols), got {self.scan_shape!r}") from None
-        if rows < 1 or cols < 1 or rows * cols >= 1 << 31:
-            raise ValueError(f"scan_shape {self.scan_shape!r}: rows and cols must be positive "
-                             "(and rows * cols below 2^31)")
-        object.__setattr__(self, "scan_shape", (rows, cols))
+        object.__setattr__(self, "scan_shape", _grid_and_window(self.scan_shape)[0])
         if self.weights is None:
             wt = neighbour_window(self.window, self.window_shape, self.std)
         else:
@@ -553,23 +593,6 @@ class NeighbourAverage:
         object.__setattr__(self, "weights", wt)
         object.__setattr__(self, "window_shape", tuple(wt.shape))
 
-    @property
-    def half(self) -> tuple[int, int]:
-        """(hr, hc): the window reaches hr scan rows and hc scan columns each way."""
-        return self.weights.shape[0] // 2, self.weights.shape[1] // 2
-
-    @property
-    def reach(self) -> int:
-        """hr * cols + hc: how far, in flat scan index, a pattern's neighbours lie from it."""
-        hr, hc = self.half
-        return hr * self.scan_shape[1] + hc
-
-    def check(self, n: int) -> None:
-        rows, cols = self.scan_shape
-        if int(n) != rows * cols:
-            raise ValueError(f"the scan has {n} patterns, scan_shape {self.scan_shape} needs "
-                             f"{rows * cols}")
-
     def _on(self, device: torch.device) -> torch.Tensor:
         """The weights on `device`, uploaded on first use."""
         wt = self._device_state.get(device)
@@ -578,21 +601,57 @@ class NeighbourAverage:
         return wt
 
 
+def _check_ring(ring, out, count: int, who: str, one_message: str | None = None):
+    """The ring and `out` of a `*_range` call; returns (cap, h, w).  A ring that is no device
+    tensor raises RuntimeError and one of the wrong dtype, shape or strides ValueError; with
+    `one_message` both raise RuntimeError with that text."""
+    on_device = torch.is_tensor(ring) and ring.is_cuda
+    laid_out = on_device and (ring.dtype == torch.float32 and ring.dim() == 4
+                              and ring.shape[1] == 1 and ring.is_contiguous())
+    if not on_device or (one_message and not laid_out):
+        raise RuntimeError(one_message or f"{who} needs a tensor on a ROCm device (no CPU fallback)")
+    if not laid_out:
+        raise ValueError(f"{who}: patterns must be a contiguous (N, 1, h, w) float32 tensor, got "
+                         f"{tuple(ring.shape)} {ring.dtype}")
+    cap, _, h, w = ring.shape
+    if not (out.is_cuda and out.is_contiguous() and out.dtype == torch.float32
+            and out.numel() >= count * h * w):
+        raise ValueError(f"out must be a contiguous float32 device tensor of at least {count} "
+                         f"({h}, {w}) patterns, got {tuple(out.shape)}")
+    return cap, h, w
+
+
+def _resident_scan(x, stage, kind: type, wanted: str, who: str) -> torch.Tensor:
+    """The resident scan x (N, 1, h, w) of `who`, checked against its record `stage` (`wanted`
+    says what it must be: a `kind`); returns x contiguous."""
+    if not isinstance(stage, kind):
+        raise TypeError(f"{wanted}, got {type(stage).__name__}")
+    if not torch.is_tensor(x) or not x.is_cuda:
+        raise RuntimeError(f"{who} needs a tensor on a ROCm device (no CPU fallback)")
+    if x.dim() != 4 or x.shape[1] != 1 or x.dtype != torch.float32:
+        raise ValueError(f"patterns must be (N, 1, h, w) float32, got {tuple(x.shape)} {x.dtype}")
+    stage.check(x.shape[0])
+    return x.contiguous()
+
+
+def _out_like(x: torch.Tensor, out: torch.Tensor | None) -> torch.Tensor:
+    """`out` if it has the resident scan's shape, a new tensor of that shape without one."""
+    if out is None:
+        return torch.empty_like(x, memory_format=torch.contiguous_format)
+    if out.shape != x.shape:
+        raise ValueError(f"out must be a {tuple(x.shape)} tensor, got {tuple(out.shape)}")
+    return out
+
+
 def average_neighbour_range(ring: torch.Tensor, neighbour_average: NeighbourAverage, p0: int,
                             count: int, out: torch.Tensor) -> torch.Tensor:
     """out[:count] = the averaged patterns [p0, p0 + count) of the scan (`ebsdvae_average_neighbours`,
     csrc/neighbour.hip).  `ring` (cap, 1, h, w) float32 holds scan pattern q in slot q % cap and
     every on-grid neighbour of the range is resident; a resident scan is its own ring (cap = N).
     `out` is contiguous, holds at least `count` patterns and does not overlap `ring`."""
-    if not (ring.is_cuda and ring.dtype == torch.float32 and ring.dim() == 4 and ring.shape[1] == 1
-            and ring.is_contiguous()):
-        raise RuntimeError("average_neighbour_range needs a contiguous (cap, 1, h, w) float32 "
-                           "tensor on a ROCm device (no CPU fallback)")
-    cap, _, h, w = ring.shape
-    if not (out.is_cuda and out.is_contiguous() and out.dtype == torch.float32
-            and out.numel() >= count * h * w):
-        raise ValueError(f"out must be a contiguous float32 device tensor of at least {count} "
-                         f"({h}, {w}) patterns, got {tuple(out.shape)}")
+    cap, h, w = _check_ring(ring, out, count, "average_neighbour_range",
+                            "average_neighbour_range needs a contiguous (cap, 1, h, w) float32 "
+                            "tensor on a ROCm device (no CPU fallback)")
     hr, hc = neighbour_average.half
     rows, cols = neighbour_average.scan_shape
     N.call("ebsdvae_average_neighbours", N.ptr(ring), cap, rows, cols, int(p0), int(count),
@@ -606,20 +665,9 @@ def average_neighbour_patterns(x: torch.Tensor, neighbour_average: NeighbourAver
     """A resident scan of transformed patterns x (N, 1, h, w) float32 on the device (what
     `ingest_patterns`, `ingest_patterns_u8` or `correct_patterns` wrote) -> a new tensor of that
     shape in which every pattern is averaged with its neighbours on the scan grid."""
-    if not isinstance(neighbour_average, NeighbourAverage):
-        raise TypeError("neighbour_average must be a NeighbourAverage, got "
-                        f"{type(neighbour_average).__name__}")
-    if not torch.is_tensor(x) or not x.is_cuda:
-        raise RuntimeError("average_neighbour_patterns needs a tensor on a ROCm device "
-                           "(no CPU fallback)")
-    if x.dim() != 4 or x.shape[1] != 1 or x.dtype != torch.float32:
-        raise ValueError(f"patterns must be (N, 1, h, w) float32, got {tuple(x.shape)} {x.dtype}")
-    neighbour_average.check(x.shape[0])
-    if out is None:
-        out = torch.empty_like(x, memory_format=torch.contiguous_format)
-    elif out.shape != x.shape:
-        raise ValueError(f"out must be a {tuple(x.shape)} tensor, got {tuple(out.shape)}")
-    return average_neighbour_range(x.contiguous(), neighbour_average, 0, x.shape[0], out)
+    x = _resident_scan(x, neighbour_average, NeighbourAverage,
+                       "neighbour_average must be a NeighbourAverage", "average_neighbour_patterns")
+    return average_neighbour_range(x, neighbour_average, 0, x.shape[0], _out_like(x, out))
 
 
 # ---------------------------------------------------------------- non-local pattern averaging
@@ -631,7 +679,7 @@ def _positive(name: str, value) -> float:
 
 
 @dataclass(frozen=True, eq=False)
-class NLPAR:
+class NLPAR(_ScanStage):
     """Non-local pattern averaging and re-weighting (Brewick, Wright and Rowenhorst,
     Ultramicroscopy 200, 2019), applied by `nlpar_patterns` and `index_scan(nlpar=...)`: every
     transformed pattern of the `scan_shape` = (rows, cols) grid becomes the weighted mean of the
@@ -650,23 +698,9 @@ class NLPAR:
     dthresh: float | None = None
 
     def __post_init__(self):
-        try:
-            rows, cols = (int(v) for v in self.scan_shape)
-        except (TypeError, ValueError):
-            raise ValueError(f"scan_shape must be (rows, cols), got {self.scan_shape!r}") from None
-        if rows < 1 or cols < 1 or rows * cols >= 1 << 31:
-            raise ValueError(f"scan_shape {self.scan_shape!r}: rows and cols must be positive "
-                             "(and rows * cols below 2^31)")
-        object.__setattr__(self, "scan_shape", (rows, cols))
-        try:
-            ny, nx = (int(v) for v in self.window_shape)
-        except (TypeError, ValueError):
-            raise ValueError(f"window_shape must be two integers, got {self.window_shape!r}") from None
-        for v in (ny, nx):
-            if not (1 <= v <= MAX_NEIGHBOUR_SIDE and v % 2 == 1):
-                raise ValueError(f"window_shape {self.window_shape!r}: sides must be odd and at most "
-                                 f"{MAX_NEIGHBOUR_SIDE}")
-        object.__setattr__(self, "window_shape", (ny, nx))
+        scan_shape, window_shape = _grid_and_window(self.scan_shape, self.window_shape)
+        object.__setattr__(self, "scan_shape", scan_shape)
+        object.__setattr__(self, "window_shape", window_shape)
         object.__setattr__(self, "lam", _positive("lam", self.lam))
         object.__setattr__(self, "sigma_floor", _positive("sigma_floor", self.sigma_floor))
         if self.sigma is not None:
@@ -678,33 +712,14 @@ class NLPAR:
             object.__setattr__(self, "dthresh", dthresh)
 
     @property
-    def half(self) -> tuple[int, int]:
-        """(hr, hc): the window reaches hr scan rows and hc scan columns each way."""
-        return self.window_shape[0] // 2, self.window_shape[1] // 2
-
-    @property
-    def reach(self) -> int:
-        """(hr + 1) * cols + (hc + 1): how far, in flat scan index, the patterns lie that a
-        pattern's weights depend on (a neighbour's variance needs that neighbour's own ring)."""
+    def schedule_half(self) -> tuple[int, int]:
+        """`half` plus one each way: a pattern's weights depend on its neighbours' variances, and
+        a variance on that neighbour's own 3 x 3 ring."""
         hr, hc = self.half
-        return (hr + 1) * self.scan_shape[1] + (hc + 1)
-
-    def check(self, n: int) -> None:
-        rows, cols = self.scan_shape
-        if int(n) != rows * cols:
-            raise ValueError(f"the scan has {n} patterns, scan_shape {self.scan_shape} needs "
-                             f"{rows * cols}")
+        return hr + 1, hc + 1
 
 
-def _nlpar_ring(ring: torch.Tensor, nlpar, who: str):
-    if not isinstance(nlpar, NLPAR):
-        raise TypeError(f"nlpar must be an NLPAR, got {type(nlpar).__name__}")
-    if not (torch.is_tensor(ring) and ring.is_cuda):
-        raise RuntimeError(f"{who} needs a tensor on a ROCm device (no CPU fallback)")
-    if not (ring.dtype == torch.float32 and ring.dim() == 4 and ring.shape[1] == 1
-            and ring.is_contiguous()):
-        raise ValueError(f"{who}: patterns must be a contiguous (N, 1, h, w) float32 tensor, got "
-                         f"{tuple(ring.shape)} {ring.dtype}")
+_WANT_NLPAR = "nlpar must be an NLPAR"
 
 
 def _nlpar_weights_range(ring: torch.Tensor, nlpar: NLPAR, p0: int, count: int):
@@ -733,12 +748,9 @@ def nlpar_range(ring: torch.Tensor, nlpar: NLPAR, p0: int, count: int,
     `ring` (cap, 1, h, w) float32 holds scan pattern q in slot q % cap, and every on-grid pattern
     within `nlpar.reach` of the range is resident; a resident scan is its own ring (cap = N).
     `out` is contiguous, holds at least `count` patterns and does not overlap `ring`."""
-    _nlpar_ring(ring, nlpar, "nlpar_range")
-    cap, _, h, w = ring.shape
-    if not (out.is_cuda and out.is_contiguous() and out.dtype == torch.float32
-            and out.numel() >= count * h * w):
-        raise ValueError(f"out must be a contiguous float32 device tensor of at least {count} "
-                         f"({h}, {w}) patterns, got {tuple(out.shape)}")
+    if not isinstance(nlpar, NLPAR):
+        raise TypeError(f"{_WANT_NLPAR}, got {type(nlpar).__name__}")
+    cap, h, w = _check_ring(ring, out, count, "nlpar_range")
     if count == 0:
         return out
     weights, _ = _nlpar_weights_range(ring, nlpar, p0, count)
@@ -748,32 +760,17 @@ def nlpar_range(ring: torch.Tensor, nlpar: NLPAR, p0: int, count: int,
     return out
 
 
-def _nlpar_scan(x, nlpar, who: str) -> torch.Tensor:
-    if not isinstance(nlpar, NLPAR):
-        raise TypeError(f"nlpar must be an NLPAR, got {type(nlpar).__name__}")
-    if not torch.is_tensor(x) or not x.is_cuda:
-        raise RuntimeError(f"{who} needs a tensor on a ROCm device (no CPU fallback)")
-    if x.dim() != 4 or x.shape[1] != 1 or x.dtype != torch.float32:
-        raise ValueError(f"patterns must be (N, 1, h, w) float32, got {tuple(x.shape)} {x.dtype}")
-    nlpar.check(x.shape[0])
-    return x.contiguous()
-
-
 def nlpar_weights(x: torch.Tensor, nlpar: NLPAR):
     """The weights NLPAR gives a resident scan x (N, 1, h, w): (weights (N, 2 hr + 1, 2 hc + 1),
     sigma (N,)) as float32 device tensors.  weights[p] is the window of pattern p before the
     normalisation, centre 1: 1 / weights[p].sum() is the share that stays on the pattern itself,
     what one looks at to choose `lam`."""
-    x = _nlpar_scan(x, nlpar, "nlpar_weights")
+    x = _resident_scan(x, nlpar, NLPAR, _WANT_NLPAR, "nlpar_weights")
     return _nlpar_weights_range(x, nlpar, 0, x.shape[0])
 
 
 def nlpar_patterns(x: torch.Tensor, nlpar: NLPAR, out: torch.Tensor | None = None) -> torch.Tensor:
     """A resident scan of transformed patterns x (N, 1, h, w) float32 on the device -> a new
     tensor of that shape (or `out`) in which every pattern is the NLPAR mean of its window."""
-    x = _nlpar_scan(x, nlpar, "nlpar_patterns")
-    if out is None:
-        out = torch.empty_like(x, memory_format=torch.contiguous_format)
-    elif out.shape != x.shape:
-        raise ValueError(f"out must be a {tuple(x.shape)} tensor, got {tuple(out.shape)}")
-    return nlpar_range(x, nlpar, 0, x.shape[0], out)
+    x = _resident_scan(x, nlpar, NLPAR, _WANT_NLPAR, "nlpar_patterns")
+    return nlpar_range(x, nlpar, 0, x.shape[0], _out_like(x, out))

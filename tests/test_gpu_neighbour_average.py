@@ -18,10 +18,7 @@ import neighbour_ref as R
 from latice import _native as N
 from latice.data_module import (NeighbourAverage, PatternCorrection, average_neighbour_patterns,
                                 average_neighbour_range, correct_patterns, ingest_patterns_u8)
-from latice.index import faiss_db as F
-from latice.index.dp_indexer import DiffractionPatternIndexer, IndexerConfig
-from latice.model import VariationalAutoEncoderRawData
-from latice.seeding import seeded_state_dict
+from scan_stage_util import clustered_indexer, same_result
 
 pytestmark = pytest.mark.gpu
 
@@ -168,51 +165,19 @@ def test_c_entry_error_returns(cuda):
 
 # ---------------------------------------------------------------- index_scan
 ROWS, COLS, SIDE = 6, 5, 140
-FIELDS = ("orientations", "success", "scores", "top_index", "n_similar", "candidate_indices",
-          "candidate_scores")
-
-
 NA_SCAN = dict(window="gaussian", window_shape=(5, 5), std=1.0)
 
 
 @pytest.fixture(scope="module")
 def indexer(cuda, tmp_path_factory):
-    """The default 128 x 128 model with seeded weights, a 6 x 5 scan of uint8 140 x 140 patterns
-    and a small clustered dictionary in the manner of tests/test_gpu_scan_index.py: 60 clusters
-    of 12 near copies, one around the latent of every scan pattern as ingested and one around
-    the latent of every averaged pattern, each with orientations scattered by 0.3 degrees around
-    its own centre.  A pattern's top match therefore lies in another cluster with the averaging
-    than without it."""
-    from scipy.spatial.transform import Rotation
-    tmp = tmp_path_factory.mktemp("neighbour")
-    m = VariationalAutoEncoderRawData()
-    m.load_state_dict({k: torch.from_numpy(v) for k, v in seeded_state_dict(0).items()})
-    m = m.to(cuda).eval()
+    """A 6 x 5 scan of uint8 140 x 140 patterns and the clustered dictionary of
+    tests/scan_stage_util.py, 60 clusters: a pattern's top match lies in another cluster with
+    the averaging than without it."""
     rng = np.random.default_rng(17)
     scan = rng.integers(0, 256, (ROWS * COLS, SIDE, SIDE), dtype=np.uint8)
-    T = ingest_patterns_u8(scan, (128, 128))
-    A = average_neighbour_patterns(T, NeighbourAverage((ROWS, COLS), **NA_SCAN))
-    with torch.no_grad():
-        centres = torch.cat([m.encode_mu(T), m.encode_mu(A)]).cpu().numpy()
-    spread = 0.05 * np.abs(centres - centres.mean(0)).mean()
-    lat, ori = [], []
-    for z in centres:
-        centre = Rotation.random(random_state=int(rng.integers(1 << 30)))
-        for _ in range(12):
-            rot = Rotation.from_rotvec(np.radians(0.3) * rng.standard_normal(3)) * centre
-            ori.append(rot.as_euler("zxz", degrees=True))
-            lat.append(z + spread * rng.standard_normal(z.shape))
-    db = F.FaissLatentVectorDatabase(F.FaissLatentVectorDatabaseConfig(dimension=16, device="cuda:0"))
-    db.add_vectors(np.array(lat, np.float32), np.array(ori))
-    cfg = IndexerConfig(pattern_path=tmp / "unused.npy", angles_path=tmp / "unused.txt",
-                        batch_size=16, device="cuda")
-    return DiffractionPatternIndexer(m, db=db, config=cfg), scan
-
-
-def _same_result(a, b, what):
-    for name in FIELDS:
-        x, y = getattr(a, name), getattr(b, name)
-        assert x.dtype == y.dtype and x.shape == y.shape and x.tobytes() == y.tobytes(), (name, what)
+    na = NeighbourAverage((ROWS, COLS), **NA_SCAN)
+    return clustered_indexer(cuda, tmp_path_factory.mktemp("neighbour"), scan,
+                             lambda T: average_neighbour_patterns(T, na), rng)
 
 
 @pytest.mark.parametrize("corrected", [False, True], ids=["plain", "corrected"])
@@ -231,12 +196,12 @@ def test_streamed_index_scan_equals_the_resident_one(indexer, corrected):
     assert len(want) == ROWS * COLS
     for b in (7, 5, 64):                  # several batches and a wrapped ring; the scan in one batch
         got = ix.index_scan(scan, neighbour_average=na, batch_size=b, **ckw, **kw)
-        _same_result(got, want, f"batch_size={b}")
+        same_result(got, want, f"batch_size={b}")
     # a transformed tensor scan takes the averaging too, and a float scan the same ingest path
-    _same_result(ix.index_scan(T, neighbour_average=na, batch_size=7, **kw), want, "tensor scan")
+    same_result(ix.index_scan(T, neighbour_average=na, batch_size=7, **kw), want, "tensor scan")
     if not corrected:
-        _same_result(ix.index_scan(scan / 255.0, neighbour_average=na, batch_size=7, **kw), want,
-                     "float64 scan")
+        same_result(ix.index_scan(scan / 255.0, neighbour_average=na, batch_size=7, **kw), want,
+                    "float64 scan")
     # the averaging is not skipped: it changes at least one pattern's top match
     plain = ix.index_scan(scan, batch_size=7, **ckw, **kw)
     assert (plain.top_index != want.top_index).any()

@@ -23,16 +23,15 @@ import numpy as np
 import pytest
 import torch
 
+import neighbour_ref as NR
 import nlpar_ref as R
 from latice import _native as N
 from latice.data_module import (NLPAR, NeighbourAverage, PatternCorrection,
-                                average_neighbour_patterns, correct_patterns, ingest_patterns,
-                                ingest_patterns_u8, nlpar_patterns, nlpar_range, nlpar_weights)
-from latice.index import faiss_db as F
-from latice.index.dp_indexer import DiffractionPatternIndexer, IndexerConfig
-from latice.model import VariationalAutoEncoderRawData
+                                average_neighbour_patterns, average_neighbour_range,
+                                correct_patterns, ingest_patterns, ingest_patterns_u8,
+                                nlpar_patterns, nlpar_range, nlpar_weights)
 from latice.patterns import _nlpar_weights_range
-from latice.seeding import seeded_state_dict
+from scan_stage_util import clustered_indexer, same_result
 
 pytestmark = pytest.mark.gpu
 
@@ -218,50 +217,71 @@ def test_out_is_honoured_and_guard_bands_stay(cuda):
     assert (gw2 == -7.0).all()
 
 
+# ---------------------------------------------------------------- the shared chain
+# (rows, cols, h, w, window, window_shape, p0, count): count None is the whole scan; a window
+# that is an array is explicit weights
+SAME_CHAIN_CASES = [
+    (5, 6, 16, 16, "circular", (3, 3), 0, None),
+    (5, 6, 16, 16, "gaussian", (5, 5), 0, None),
+    (5, 6, 16, 16, "rectangular", (3, 5), 0, None),
+    (5, 6, 16, 16, "rectangular", (5, 3), 0, None),
+    (5, 6, 16, 16, "rectangular", (1, 1), 0, None),
+    (3, 11, 8, 12, "circular", (5, 5), 0, None),        # runs of 8 + 3 columns
+    (1, 7, 16, 16, "rectangular", (5, 5), 0, None),     # line scans
+    (7, 1, 16, 16, "rectangular", (5, 5), 0, None),
+    (5, 6, 16, 16, "gaussian", (5, 5), 7, 16),          # both ends of the range clip a run
+    # on-grid neighbour rows whose weights are all zero: the fixed averaging does not load them
+    (5, 6, 16, 16, ((0, 0, 0), (1, 2, 0.5), (0, 0, 0)), (3, 3), 0, None),
+    (5, 6, 16, 16, ((0, 3, 0), (0, 0, 0), (1, 2, 1), (0, 0, 0), (0, 0, 0)), (5, 3), 7, 16),
+]
+
+
+@pytest.mark.parametrize("rows,cols,h,w,window,shape,p0,count", SAME_CHAIN_CASES)
+def test_average_with_fixed_weights_is_the_fixed_averaging(cuda, rows, cols, h, w, window, shape,
+                                                           p0, count):
+    """ebsdvae_nlpar_average with the per-output weights W[a][b] where the tap is on the grid
+    and 0 where it is off gives the bytes of ebsdvae_average_neighbours with W: a dropped tap
+    enters both chains as weight 0, and for finite patterns fma(0, t, s) == s."""
+    count = rows * cols - p0 if count is None else count
+    if isinstance(window, str):
+        na = NeighbourAverage((rows, cols), window=window, window_shape=shape, std=1.0)
+    else:
+        na = NeighbourAverage((rows, cols), weights=np.array(window, np.float32))
+    (hr, hc), W = na.half, na.weights
+    assert W.shape == shape
+    x = torch.from_numpy(NR.patterns(rows * cols, h, w, seed=rows * 100 + cols)).to(cuda)
+    i, j = np.divmod(np.arange(p0, p0 + count), cols)
+    per_output = np.zeros((count,) + W.shape, np.float32)
+    for a in range(-hr, hr + 1):
+        for b in range(-hc, hc + 1):
+            on = (i + a >= 0) & (i + a < rows) & (j + b >= 0) & (j + b < cols)
+            per_output[on, a + hr, b + hc] = W[a + hr, b + hc]
+    want = torch.full((count + 1, 1, h, w), -7.0, device=cuda)
+    average_neighbour_range(x, na, p0, count, want)
+    got = torch.full((count + 1, 1, h, w), -7.0, device=cuda)
+    N.call("ebsdvae_nlpar_average", N.ptr(x), rows * cols, rows, cols, p0, count,
+           N.ptr(torch.from_numpy(per_output).to(cuda)), hr, hc, h, w, N.ptr(got), N.stream(cuda))
+    got, want = got.cpu().numpy(), want.cpu().numpy()
+    assert got.tobytes() == want.tobytes()
+    assert (got[count:] == -7.0).all() and np.isfinite(got[:count]).all()
+    if rows * cols > 1 and shape != (1, 1):
+        assert np.abs(got[:count] - x.cpu().numpy()[p0:p0 + count]).max() > 0.01   # it averaged
+
+
 # ---------------------------------------------------------------- index_scan
 ROWS, COLS, SIDE = 6, 7, 140
-FIELDS = ("orientations", "success", "scores", "top_index", "n_similar", "candidate_indices",
-          "candidate_scores")
 NL_SCAN = dict(window_shape=(3, 5), lam=0.9)
 
 
 @pytest.fixture(scope="module")
 def indexer(cuda, tmp_path_factory):
-    """The default 128 x 128 model with seeded weights, the two-grain 6 x 7 scan as uint8
-    140 x 140 detector patterns, and a small clustered dictionary in the manner of
-    tests/test_gpu_neighbour_average.py: clusters of 12 near copies around the latent of every
-    scan pattern as ingested and of every NLPAR-averaged one, each with orientations scattered
-    by 0.3 degrees around its own centre."""
-    from scipy.spatial.transform import Rotation
-    tmp = tmp_path_factory.mktemp("nlpar")
-    m = VariationalAutoEncoderRawData()
-    m.load_state_dict({k: torch.from_numpy(v) for k, v in seeded_state_dict(0).items()})
-    m = m.to(cuda).eval()
-    rng = np.random.default_rng(23)
+    """The two-grain 6 x 7 scan as uint8 140 x 140 detector patterns and the clustered
+    dictionary of tests/scan_stage_util.py around the latents of the scan as ingested and as
+    NLPAR-averaged."""
     scan = np.round(R.nlpar_scan(ROWS, COLS, SIDE, SIDE)[:, 0] * 255.0).astype(np.uint8)
-    T = ingest_patterns_u8(scan, (128, 128))
-    A = nlpar_patterns(T, NLPAR((ROWS, COLS), **NL_SCAN))
-    with torch.no_grad():
-        centres = torch.cat([m.encode_mu(T), m.encode_mu(A)]).cpu().numpy()
-    spread = 0.05 * np.abs(centres - centres.mean(0)).mean()
-    lat, ori = [], []
-    for z in centres:
-        centre = Rotation.random(random_state=int(rng.integers(1 << 30)))
-        for _ in range(12):
-            rot = Rotation.from_rotvec(np.radians(0.3) * rng.standard_normal(3)) * centre
-            ori.append(rot.as_euler("zxz", degrees=True))
-            lat.append(z + spread * rng.standard_normal(z.shape))
-    db = F.FaissLatentVectorDatabase(F.FaissLatentVectorDatabaseConfig(dimension=16, device="cuda:0"))
-    db.add_vectors(np.array(lat, np.float32), np.array(ori))
-    cfg = IndexerConfig(pattern_path=tmp / "unused.npy", angles_path=tmp / "unused.txt",
-                        batch_size=16, device="cuda")
-    return DiffractionPatternIndexer(m, db=db, config=cfg), scan
-
-
-def _same_result(a, b, what):
-    for name in FIELDS:
-        x, y = getattr(a, name), getattr(b, name)
-        assert x.dtype == y.dtype and x.shape == y.shape and x.tobytes() == y.tobytes(), (name, what)
+    nl = NLPAR((ROWS, COLS), **NL_SCAN)
+    return clustered_indexer(cuda, tmp_path_factory.mktemp("nlpar"), scan,
+                             lambda T: nlpar_patterns(T, nl), np.random.default_rng(23))
 
 
 @pytest.mark.parametrize("corrected", [False, True], ids=["plain", "corrected"])
@@ -283,9 +303,9 @@ def test_streamed_index_scan_equals_the_resident_one(indexer, staging, corrected
     assert len(want) == ROWS * COLS
     for b in (7, 5, 64):                  # several batches and a wrapped ring; the scan in one batch
         got = ix.index_scan(scan, nlpar=nl, batch_size=b, **ckw, **kw)
-        _same_result(got, want, f"batch_size={b}")
+        same_result(got, want, f"batch_size={b}")
     # a transformed tensor scan takes it too
-    _same_result(ix.index_scan(T, nlpar=nl, batch_size=7, **kw), want, "tensor scan")
+    same_result(ix.index_scan(T, nlpar=nl, batch_size=7, **kw), want, "tensor scan")
     # it is not skipped: the scores differ from the plain scan's
     plain = ix.index_scan(scan, batch_size=7, **ckw, **kw)
     assert plain.scores.tobytes() != want.scores.tobytes()
