@@ -34,8 +34,8 @@ int check_launch(const char* what) {
 
 extern "C" const char* ebsdvae_last_error(void) { return g_err; }
 // ABI version (include/ebsdvae.h EBSDVAE_ABI_VERSION): 2 since the heads entry points took
-// their caller-owned `work` scratch (round 4), 3 with the scan maps (csrc/scan_maps.hip);
-// latice/_native.load() refuses any other value
+// their caller-owned `work` scratch (round 4), 3 with the scan maps (csrc/scan_maps.hip),
+// 4 with the grains (csrc/grains.hip); latice/_native.load() refuses any other value
 extern "C" int ebsdvae_version(void) { return EBSDVAE_ABI_VERSION; }
 
 // ------------------------------------------------------------------ cross-stream ordering

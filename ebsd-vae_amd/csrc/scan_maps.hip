@@ -17,7 +17,8 @@
 //   kam_kernel   one thread per scan point: the cubic disorientation to each on-grid neighbour in
 //                row-major offset order, the consensus kernel's min over the 24 equivalents
 //                (csrc/orient.hip), a float64 sum in that order and one division.
-#include "orient_math.h"
+// cubic_op, finite3 and map_offset are shared with grains.hip: scan_grid.h.
+#include "scan_grid.h"
 #include "../../include/ebsdvae.h"
 
 #include <math.h>
@@ -26,10 +27,6 @@ namespace ev {
 
 constexpr int kMapThreads = 256;
 constexpr int kMapWaves = kMapThreads / 64;
-
-EV_DEVINL Q4 cubic_op(int c) {
-  return qnormalize(Q4{kCubic[c][0], kCubic[c][1], kCubic[c][2], kCubic[c][3]});
-}
 
 // scipy Rotation.as_matrix of a unit quaternion
 EV_DEVINL void qmatrix(const Q4& q, double m[3][3]) {
@@ -46,10 +43,6 @@ EV_DEVINL void qmatrix(const Q4& q, double m[3][3]) {
   m[0][2] = 2.0 * (xz + yw);
   m[1][2] = 2.0 * (yz - xw);
   m[2][2] = -x2 - y2 + z2 + w2;
-}
-
-EV_DEVINL bool finite3(double a, double b, double c) {
-  return isfinite(a) && isfinite(b) && isfinite(c);
 }
 
 // a colour channel 255 v / max as 8 bits, ties to even as Python's round; what is not a number
@@ -111,11 +104,6 @@ __global__ __launch_bounds__(kMapThreads) void ipf_kernel(const double* __restri
   out[0] = ipf_level(r, mx);
   out[1] = ipf_level(g, mx);
   out[2] = ipf_level(b, mx);
-}
-
-// the (a, b) offsets of a connectivity, row-major: 4 = the cross, 8 = the square
-EV_DEVINL bool map_offset(int connectivity, int a, int b) {
-  return (a != 0 || b != 0) && (connectivity == 8 || a == 0 || b == 0);
 }
 
 __global__ __launch_bounds__(kMapThreads) void osm_kernel(const long long* __restrict__ cand,

@@ -121,26 +121,28 @@ SIGNATURES = {
     "ebsdvae_ipf_colors": [P, I64, I, P, P],
     "ebsdvae_orientation_similarity": [P, I, I, I, I, I, P, P],
     "ebsdvae_kernel_misorientation": [P, I, I, I, ctypes.c_double, P, P],
+    "ebsdvae_grain_work": [I, I],
+    "ebsdvae_segment_grains": [P, P, I, I, I, ctypes.c_double, P, P, P, P, P, P, P],
 }
 _RESTYPE = {"ebsdvae_last_error": ctypes.c_char_p, "ebsdvae_wgrad_reduce_work": ctypes.c_size_t,
             "ebsdvae_wgrad_reduce_batch_work": ctypes.c_size_t,
             "ebsdvae_cosine_topk_work": ctypes.c_size_t,
             "ebsdvae_index_latents_work": ctypes.c_size_t,
             "ebsdvae_correct_patterns_work": ctypes.c_size_t,
-            "ebsdvae_nlpar_work": ctypes.c_size_t,
+            "ebsdvae_nlpar_work": ctypes.c_size_t, "ebsdvae_grain_work": ctypes.c_size_t,
             "ebsdvae_heads_wgrad_work": ctypes.c_size_t, "ebsdvae_heads_work": ctypes.c_size_t, "ebsdvae_pack_split_bytes": ctypes.c_size_t}
 # queries that return a value rather than a status
 QUERIES = {"ebsdvae_version", "ebsdvae_conv_first_stat_tiles", "ebsdvae_conv3x3_stat_tiles", "ebsdvae_conv3x3_wgrad_slices",
            "ebsdvae_wgrad_reduce_batch_work", "ebsdvae_cosine_topk_work",
            "ebsdvae_index_latents_work", "ebsdvae_correct_patterns_work", "ebsdvae_nlpar_work",
-           "ebsdvae_in_bwd_tiles", "ebsdvae_in_bwd_apply_tiles", "ebsdvae_in_bwd_final_tiles", "ebsdvae_wgrad_reduce_work", "ebsdvae_heads_wgrad_work", "ebsdvae_heads_work",
+           "ebsdvae_grain_work", "ebsdvae_in_bwd_tiles", "ebsdvae_in_bwd_apply_tiles", "ebsdvae_in_bwd_final_tiles", "ebsdvae_wgrad_reduce_work", "ebsdvae_heads_wgrad_work", "ebsdvae_heads_work",
            "ebsdvae_conv3x3_split_supported", "ebsdvae_conv3x3_split_stat_tiles",
            "ebsdvae_conv3x3_split_pool_ok", "ebsdvae_conv3x3_fwd_split_first_ok",
            "ebsdvae_pack_split_bytes", "ebsdvae_conv3x3_wgrad_split_slices", "ebsdvae_net_end_tiles",
            "ebsdvae_conv3x3_dwgrad_slices", "ebsdvae_conv3x3_dwgrad_stat_tiles"}
 
 # include/ebsdvae.h EBSDVAE_ABI_VERSION: the signatures above
-ABI_VERSION = 3
+ABI_VERSION = 4
 
 _lib = None
 _lock = threading.Lock()

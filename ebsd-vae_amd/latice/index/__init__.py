@@ -7,7 +7,9 @@ HIP kernels (csrc/search.hip, csrc/orient.hip; fused for whole scans in csrc/sca
 `DiffractionPatternIndexer.index_scan`).  Other reference modules of this package
 (chroma_db, latent_embedding) resolve from LATICE_REFERENCE_ROOT (see latice/__init__.py).
 `maps` holds the scan maps built from an indexed scan's result rows (csrc/scan_maps.hip): IPF
-colours, the orientation similarity map and the kernel average misorientation.
+colours, the orientation similarity map and the kernel average misorientation; `grains` the grain
+segmentation of such a scan with the grain mean orientation, GROD, GOS and the boundary map
+(csrc/grains.hip).
 """
 from latice import _extend_path
 
@@ -15,6 +17,7 @@ _extend_path(__path__, "index")
 
 from latice.index.maps import (ScanMaps, ipf_colors, kernel_average_misorientation,  # noqa: E402
                                orientation_similarity_map)
+from latice.index.grains import GrainMap, segment_grains  # noqa: E402
 
 __all__ = ["ScanMaps", "ipf_colors", "kernel_average_misorientation",
-           "orientation_similarity_map"]
+           "orientation_similarity_map", "GrainMap", "segment_grains"]

@@ -46,6 +46,7 @@ from latice.data_module import DPDataModule, PatternTransform, create_default_tr
 from latice.index.faiss_db import (MAX_K, FaissLatentVectorDatabase,
                                    FaissLatentVectorDatabaseConfig, LatentIndexResult,
                                    OrientationResult)
+from latice.index.grains import GrainMap, grain_rows
 from latice.index.maps import (IPF_DIRECTIONS, ScanMaps, ipf_rows, misorientation_rows,
                                similarity_rows)
 from latice.index.scan import (SCAN_F32, SCAN_F64, SCAN_U8, ScanIndexResult, neighbour_schedule,
@@ -112,19 +113,28 @@ def _result_buffer(n: int, k: int, candidates: bool, dev, maps: ScanMaps | None 
     of ONE device buffer, so one copy brings them all back; with `maps`, the scan maps are
     further fields of it.  Returns (the buffer, its layout [(name, dtype, shape, byte offset,
     bytes)], the index fields as a `LatentIndexResult`, the map fields by name)."""
+    grains = maps is not None and maps.grains
     # the 8-byte fields come first to keep every view aligned, the bytes last
     fields = [("best", torch.float64, (n, 3)), ("row", torch.int64, (n,))]
     fields += [("cand_idx", torch.int64, (n, k))] if candidates else []
+    # the grains' only 8-byte field sits with the 8-byte group; without grains nothing moves
+    map_fields = [("grain_orientation", torch.float64, (n, 3))] if grains else []
+    fields += map_fields
     fields += [("score", torch.float32, (n,)), ("success", torch.int32, (n,)),
                ("n_similar", torch.int32, (n,))]
     fields += [("cand_scores", torch.float32, (n, k))] if candidates else []
-    map_fields = []
+    tail_fields = []
     if maps is not None:
-        map_fields += [("osm", torch.float32, (n,))] if maps.similarity else []
-        map_fields += [("kam", torch.float32, (n,))] if maps.kam else []
-        map_fields += [("ipf_" + d, torch.uint8, (n, 3)) for d in maps.ipf]
+        tail_fields += [("osm", torch.float32, (n,))] if maps.similarity else []
+        tail_fields += [("kam", torch.float32, (n,))] if maps.kam else []
+        if grains:
+            tail_fields += [("grain_id", torch.int32, (n,)), ("gos", torch.float32, (n,)),
+                            ("grod", torch.float32, (n,))]
+        tail_fields += [("ipf_" + d, torch.uint8, (n, 3)) for d in maps.ipf]
+        tail_fields += [("grain_boundary", torch.uint8, (n,))] if grains else []
+    map_fields = map_fields + tail_fields
     layout, end = [], 0
-    for name, dt, shape in fields + map_fields:
+    for name, dt, shape in fields + tail_fields:
         nbytes = int(np.prod(shape)) * torch.empty((), dtype=dt).element_size()
         layout.append((name, dt, shape, end, nbytes))
         end += nbytes
@@ -149,12 +159,18 @@ def _unpack_result(buf: torch.Tensor, layout, maps: ScanMaps | None = None) -> S
             result.orientation_similarity = h["osm"].reshape(grid)
         if maps.kam:
             result.kam = h["kam"].reshape(grid)
+        if maps.grains:
+            result.grains = GrainMap(grain_id=h["grain_id"].reshape(grid),
+                                     grain_orientation=h["grain_orientation"].reshape(grid + (3,)),
+                                     gos=h["gos"].reshape(grid), grod=h["grod"].reshape(grid),
+                                     boundary=h["grain_boundary"].reshape(grid))
     return result
 
 
-def _run_maps(maps: ScanMaps, res: LatentIndexResult, views: dict) -> None:
+def _run_maps(maps: ScanMaps, res: LatentIndexResult, views: dict):
     """The scan maps of the whole scan's result rows `res` into their fields `views` of the result
-    buffer, on the current stream: behind the last batch, in front of the copy back."""
+    buffer, on the current stream: behind the last batch, in front of the copy back.  Returns the
+    grains' device scratch (None without grains), to be kept until the copy back."""
     for d in maps.ipf:
         ipf_rows(res.best, IPF_DIRECTIONS[d], views["ipf_" + d])
         if maps.mask_failed:
@@ -165,6 +181,12 @@ def _run_maps(maps: ScanMaps, res: LatentIndexResult, views: dict) -> None:
     if maps.kam:
         misorientation_rows(res.best, maps.scan_shape, maps.connectivity, maps.kam_max_angle,
                             views["kam"])
+    if maps.grains:
+        return grain_rows(res.best, res.success if maps.grain_mask_failed else None,
+                          maps.scan_shape, maps.connectivity, maps.grain_threshold,
+                          views["grain_id"], views["grain_orientation"], views["gos"],
+                          views["grod"], views["grain_boundary"])
+    return None
 
 
 class DiffractionPatternIndexer:
@@ -312,7 +334,9 @@ class DiffractionPatternIndexer:
         are further fields of the one result buffer (still one copy back and one host wait) and
         of the `ScanIndexResult`.  The similarity map needs every pattern's candidate rows on
         the device: without `return_candidates` they live in a device tensor that is not copied
-        back.  Without `maps` nothing runs differently."""
+        back.  With `maps.grains` the grain segmentation (latice/index/grains.py) follows them the
+        same way and comes back as `ScanIndexResult.grains`.  Without `maps` nothing runs
+        differently."""
         _check_raw_stage("resample", resample, DetectorResample, patterns)
         if nlpar is not None and not isinstance(nlpar, NLPAR):
             raise TypeError(f"nlpar must be an NLPAR, got {type(nlpar).__name__}")
@@ -403,7 +427,7 @@ class DiffractionPatternIndexer:
 
         if maps is not None:
             with torch.cuda.device(dev):
-                _run_maps(maps, res, map_views)
+                staging = (staging, _run_maps(maps, res, map_views))   # and the grains' scratch
         result = _unpack_result(buf, layout, maps)     # the host's only wait
         del staging                  # every copy-stream buffer outlived its last consumer
         return result

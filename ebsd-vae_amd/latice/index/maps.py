@@ -30,7 +30,7 @@ __all__ = ["IPF_DIRECTIONS", "MAX_SIMILARITY_K", "ScanMaps", "ipf_colors",
 IPF_DIRECTIONS = {"x": 0, "y": 1, "z": 2}     # the row of the rotation matrix: ipf_x / _y / _z
 MAX_SIMILARITY_K = 64                         # candidates per point: one wave lane each
 CONNECTIVITIES = (4, 8)
-N_NUMPY = {torch.float64: np.float64, torch.int64: np.int64}
+N_NUMPY = {torch.float64: np.float64, torch.int64: np.int64, torch.int32: np.int32}
 
 
 def _scan_shape(scan_shape) -> tuple[int, int]:
@@ -61,6 +61,17 @@ def _max_angle(max_angle) -> float:
     if math.isnan(v) or v < 0.0:
         raise ValueError(f"max_angle must be a non-negative number of degrees (inf or None keeps "
                          f"every neighbour), got {max_angle!r}")
+    return v
+
+
+def _grain_threshold(threshold) -> float:
+    try:
+        v = float(threshold)
+    except (TypeError, ValueError):
+        v = math.nan
+    if not math.isfinite(v) or v < 0.0:
+        raise ValueError(f"the grain threshold must be a finite, non-negative number of degrees, "
+                         f"got {threshold!r}")
     return v
 
 
@@ -198,7 +209,10 @@ class ScanMaps:
     ()); `similarity` asks for `orientation_similarity_map` (divided by k with
     `similarity_normalize`), `kam` for `kernel_average_misorientation` within `kam_max_angle`
     degrees (None or inf: every neighbour); both use `connectivity` 4 or 8.  With `mask_failed`
-    the colours of patterns without a consensus (`success` false) are (0, 0, 0)."""
+    the colours of patterns without a consensus (`success` false) are (0, 0, 0).  `grains` asks
+    for `segment_grains` (latice/index/grains.py) at `grain_threshold` degrees and the same
+    `connectivity`, with every output, as `ScanIndexResult.grains`; with `grain_mask_failed` the
+    patterns without a consensus are unusable points (grain id -1)."""
 
     scan_shape: tuple
     ipf: tuple = ("z",)
@@ -208,6 +222,9 @@ class ScanMaps:
     kam_max_angle: float | None = 5.0
     connectivity: int = 4
     mask_failed: bool = False
+    grains: bool = False
+    grain_threshold: float = 5.0
+    grain_mask_failed: bool = False
 
     def __post_init__(self):
         object.__setattr__(self, "scan_shape", _scan_shape(self.scan_shape))
@@ -222,7 +239,9 @@ class ScanMaps:
         object.__setattr__(self, "ipf", ipf)
         object.__setattr__(self, "connectivity", _connectivity(self.connectivity))
         object.__setattr__(self, "kam_max_angle", _max_angle(self.kam_max_angle))
-        for name in ("similarity", "similarity_normalize", "kam", "mask_failed"):
+        object.__setattr__(self, "grain_threshold", _grain_threshold(self.grain_threshold))
+        for name in ("similarity", "similarity_normalize", "kam", "mask_failed", "grains",
+                     "grain_mask_failed"):
             object.__setattr__(self, name, bool(getattr(self, name)))
 
     def check(self, n: int) -> None:

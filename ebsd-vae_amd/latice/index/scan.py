@@ -29,6 +29,7 @@ class ScanIndexResult:
     ipf_colors: dict | None = None                # direction -> (rows, cols, 3) uint8
     orientation_similarity: np.ndarray | None = None   # (rows, cols) float32
     kam: np.ndarray | None = None                 # (rows, cols) float32, degrees
+    grains: object | None = None                  # GrainMap (latice/index/grains.py) of numpy arrays
 
     def __len__(self) -> int:
         return int(self.success.shape[0])

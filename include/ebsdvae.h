@@ -39,9 +39,10 @@ const char* ebsdvae_last_error(void);
 /* ABI version of this header; ebsdvae_version() returns the library's.  Bumped on every
  * incompatible signature change (2: ebsdvae_heads_fwd / _bwd / ebsdvae_latent_mu take a
  * caller-owned `work` scratch pointer; 3: the scan maps, ebsdvae_ipf_colors /
- * ebsdvae_orientation_similarity / ebsdvae_kernel_misorientation, which the binding requires).
+ * ebsdvae_orientation_similarity / ebsdvae_kernel_misorientation, which the binding requires;
+ * 4: the grains, ebsdvae_grain_work / ebsdvae_segment_grains, which the binding requires).
  * Callers must check it before the first call. */
-#define EBSDVAE_ABI_VERSION 3
+#define EBSDVAE_ABI_VERSION 4
 int ebsdvae_version(void);
 
 /* ---- stream ordering ------------------------------------------------------------------
@@ -736,6 +737,54 @@ int ebsdvae_orientation_similarity(const long long* cand_idx, int k, int rows, i
                                    ebsdvae_stream_t stream);
 int ebsdvae_kernel_misorientation(const double* euler, int rows, int cols, int connectivity,
                                   double max_deg, float* kam, ebsdvae_stream_t stream);
+
+/* ---- grains ("Grains") --------------------------------------------
+ * Grain segmentation of a scan and what is read off its grains: the grain mean orientation, the
+ * grain reference orientation deviation (GROD), the grain orientation spread (GOS) and the grain
+ * boundary.  The grid, its neighbours, the arithmetic (float64) and the 24 operators S of QUAT_SYM
+ * are those of the scan maps above.
+ *
+ * Input: euler (rows * cols, 3) float64, ZXZ degrees, row-major; valid (rows * cols,) int32 or
+ * NULL (= all); connectivity 4 or 8; threshold_deg >= 0, finite.
+ * Usable points: the three angles are finite and valid (if given) is non-zero.
+ * Edges: two usable neighbours p < q (flat indices) are joined iff
+ *   min over the 24 S, in order, of |conj(q_p) (S q_q)| in degrees <= threshold_deg,
+ * ebsdvae_kernel_misorientation's disorientation.  Each edge is evaluated ONCE, with p the lower
+ * flat index, never from both ends (the two could differ in the last ulp and disagree at the
+ * threshold).  The forward neighbours of a point are right and below (connectivity 4), or right,
+ * below-left, below and below-right (8).
+ * Grains are the connected components of that graph.  grain_id (int32): a usable point gets the
+ * rank of its grain when the grains are ordered by their first point in row-major order
+ * (0 .. G - 1); an unusable point gets -1.  A usable point without an accepted edge is a grain of
+ * one.
+ * Grain mean orientation (the projection-to-reference mean): the grain's root is its lowest flat
+ * index, with quaternion q_r.  Every member q_p is replaced by the equivalent S q_p with the
+ * smallest |conj(q_r) (S q_p)| (the first S in QUAT_SYM order on a tie: strict <), negated if its
+ * 4-component dot product with q_r is negative; each component is rounded to a multiple of 2^-31
+ * and the components are summed as 64-bit integers, so the sum does not depend on the order of
+ * addition.  The mean m is that sum normalised; grain_euler (rows * cols, 3) float64 holds
+ * as_euler("zxz", degrees) of m at every member of the grain, NaN at unusable points.
+ * GROD: grod[p] = float32(min over the 24 S of |conj(q_p) (S m)| in degrees); NaN at unusable
+ * points.
+ * GOS: gos[p] = float32(the mean over p's grain of its members' float64 GROD, each rounded to a
+ * multiple of 2^-24 degrees and summed as 64-bit integers), at every member; NaN at unusable
+ * points.
+ * Boundary: boundary[p] (uint8) = 1 iff p is usable and some on-grid neighbour under connectivity
+ * (all 4 or 8 of them) has a different grain_id, -1 counting as different; else 0.
+ * Every output is a function of the inputs alone, bit for bit, whatever `work` held.
+ *
+ * grain_id is required; grain_euler, gos, grod and boundary may each be NULL, and then are not
+ * computed (gos without grod: the GROD is computed and not stored).  work:
+ * ebsdvae_grain_work(rows, cols) bytes of caller-owned device scratch, 8-byte aligned, which may
+ * hold anything; the query returns 0 for a grid the entry point refuses.
+ * Nonzero, and nothing launched or written, for a null euler, grain_id or work, a misaligned work,
+ * rows or cols < 1, rows * cols >= 2^31, a connectivity other than 4 or 8, or a threshold_deg that
+ * is NaN, negative or infinite. */
+size_t ebsdvae_grain_work(int rows, int cols);
+int ebsdvae_segment_grains(const double* euler, const int* valid, int rows, int cols,
+                           int connectivity, double threshold_deg, int* grain_id,
+                           double* grain_euler, float* gos, float* grod, unsigned char* boundary,
+                           void* work, ebsdvae_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -14,6 +14,13 @@ uint8 patterns at 140 x 140 in pinned memory, here a 128 x 128 grid, 1,048,576 d
 top_n = 20) without maps, with the default map (IPF z) and with every map (three IPF directions,
 similarity, KAM, connectivity 8), alternating the three in one process.
 
+The grains leg (`ebsdvae_segment_grains`, csrc/grains.hip) runs on the same --grid scan in three
+shapes: (a) the 50 x 50-point grains above at 5 degrees, (b) one grain filling the scan, the worst
+case for contention on the per-grain accumulators, and (c) every point its own grain (threshold 0
+on the noisy data); each at both connectivities, once with every output and once with the ids
+only, beside the KAM time at the same connectivity from the same run.  The whole-scan comparison
+gets a fourth variant, every map plus grains.
+
 --maps-only skips the scans.
 
 Prints one JSON line.  Needs a ROCm GPU: there is no CPU path.
@@ -73,6 +80,7 @@ def main():
     if n % a.cols:
         raise SystemExit(f"scan_maps_rate: {n} patterns do not fill rows of {a.cols}")
 
+    from latice import _native as N
     from latice.index.maps import ScanMaps, ipf_rows, misorientation_rows, similarity_rows
 
     logging.getLogger("latice").setLevel(logging.ERROR)
@@ -104,7 +112,30 @@ def main():
     per_map["similarity_mean"] = round(float(f32.mean()), 3)
     misorientation_rows(euler, (g, g), 4, 5.0, f32)
     per_map["kam_mean_deg"] = round(float(f32.mean()), 4)
-    del euler, cand, rgb, f32
+
+    # ---- grains: three shapes x two connectivities x (every output, ids only)
+    from latice.index.grains import grain_rows
+    one = torch.from_numpy((base[0] + rng.uniform(-0.5, 0.5, (pts, 3)))).to(dev)
+    ids = torch.empty(pts, dtype=torch.int32, device=dev)
+    outs = dict(grain_euler=torch.empty(pts, 3, dtype=torch.float64, device=dev),
+                gos=torch.empty(pts, dtype=torch.float32, device=dev),
+                grod=torch.empty(pts, dtype=torch.float32, device=dev),
+                boundary=torch.empty(pts, dtype=torch.uint8, device=dev))
+    work = torch.empty(N.call("ebsdvae_grain_work", g, g), dtype=torch.uint8, device=dev)
+    grains = {}
+    for shape_name, e, thr in (("grains_50x50", euler, 5.0), ("one_grain", one, 5.0),
+                               ("every_point", euler, 0.0)):
+        for conn in (4, 8):
+            for what, kw_out in (("all", outs), ("ids", {})):
+                fn = lambda: grain_rows(e, None, (g, g), conn, thr, ids, work=work, **kw_out)  # noqa: E731
+                fn()
+                torch.cuda.synchronize()
+                key = f"{shape_name}_{conn}_{what}"
+                grains[key + "_ms"] = round(_events(fn), 4)
+                grains[key + "_over_kam"] = round(grains[key + "_ms"] / per_map[f"kam_{conn}_ms"], 3)
+            grains[f"{shape_name}_{conn}_n_grains"] = int(ids.max()) + 1
+    per_map["grains"] = grains
+    del euler, cand, rgb, f32, one, ids, outs, work
 
     out = {"tool": "scan_maps_rate", "grid": [g, g], "top_n": k, "copy_tbs": a.copy_tbs,
            "per_map": per_map}
@@ -135,6 +166,8 @@ def main():
         kw = dict(top_n=a.top_n, orientation_threshold=1.0, min_required_matches=18)
         shape = (n // a.cols, a.cols)
         every = ScanMaps(shape, ipf=("x", "y", "z"), similarity=True, kam=True, connectivity=8)
+        with_grains = ScanMaps(shape, ipf=("x", "y", "z"), similarity=True, kam=True, connectivity=8,
+                               grains=True)
 
         def timed(fn):
             torch.cuda.synchronize()
@@ -146,7 +179,9 @@ def main():
         runs = {"index_scan": lambda: ix.index_scan(scan, batch_size=a.batch, **kw),
                 "index_scan_ipf_z": lambda: ix.index_scan(scan, batch_size=a.batch,
                                                           maps=ScanMaps(shape), **kw),
-                "index_scan_every_map": lambda: ix.index_scan(scan, batch_size=a.batch, maps=every, **kw)}
+                "index_scan_every_map": lambda: ix.index_scan(scan, batch_size=a.batch, maps=every, **kw),
+                "index_scan_every_map_grains": lambda: ix.index_scan(scan, batch_size=a.batch,
+                                                                     maps=with_grains, **kw)}
         for fn in runs.values():                         # warm-up: every shape of the timed window
             fn()
         times = {name: [] for name in runs}
