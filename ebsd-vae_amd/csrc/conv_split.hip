@@ -15,7 +15,11 @@
 //
 // GEMM view as in conv_fwd.hip: M = output pixels, N = Cout, K = 9 taps x Cin swept in
 // 8-channel chunks.  One 32x32x16 k-step covers two taps: lane half h = lane >> 5 takes tap
-// 2s + h (s = 0..4; a zero tenth tap pads the odd tap count).
+// 2s + h (s = 0..3), every product of the list above one MFMA.  K-step 4 has tap 8 alone, so
+// its lane halves carry different piece products of tap 8 instead (split_apiece / split_wrow
+// below): 2 MFMAs for NP = 2 (a1b0 | a0b1, then a0b0 | the pack's zero tenth tap), 3 for NP = 3
+// (all six products, two per MFMA) -- 14 / 27 MFMAs per chunk and fragment pair, where 15 / 30
+// would multiply the zero tap in half of every k-step-4 instruction.
 //   LDS halo record per pixel (48 B): piece 0 [8 ch] | piece 1 [8 ch] | piece 2 or pad ->
 //     one ds_read_b128 per piece, conflict-free over 16 consecutive pixels (3 x 16 B granules
 //     apart);
@@ -61,7 +65,8 @@ EV_DEVINL void split_bf16(float x, __bf16 (&p)[NP]) {
 //     x0 = f16(x), x1 = f16(x - x0)      (11 significand bits each, |x - x0 - x1| <= 2^-23 |x|
 //                                          for normal x1, 2^-25 absolute below it)
 // and the three products a0b0 + a0b1 + a1b0 on v_mfma_f32_32x32x16_f16 (the dropped a1b1 is
-// <= 2^-24 relative): ~2^-22.5 per product, at the bf16x3 rate.  fp16's range is narrow, so
+// <= 2^-24 relative): ~2^-22.5 per product, at the bf16x3 rate (tap 8's two cross products
+// share one MFMA, as for NP = 2 above).  fp16's range is narrow, so
 // the weights of each layer are packed as w * 2^k, k from the layer's max |w| (max |w| 2^k in
 // [2^11, 2^12): pack_wmax_kernel + pack_split_kernel, stored in the pack's trailer) and the
 // epilogue multiplies the accumulators by the exact 2^-k.  Forward operands are normalised
@@ -120,6 +125,55 @@ EV_DEVINL f32x16 mfma_piece(bf16x8 a, bf16x8 b, f32x16 c) {
 
 EV_DEVINL bf16x8 lds_frag(const char* p) { return *reinterpret_cast<const bf16x8*>(p); }
 
+// Fragment slots of k-step s (both split kernels; NPC pieces per operand, hk = lane half).
+// K-steps 0..3 hold two taps: slot i is piece i of tap 2s + hk on both sides.  K-step 4 holds
+// tap 8 alone (toff[4] points both lane halves at its pixels), so the hk = 1 half carries
+// further products of tap 8 instead of a zero tenth tap; slot i x slot i then sums
+//   NPC = 2:  slot 1  (a1 | a0) x (b0 | b1) = a1b0 + a0b1      (hk = 0 | hk = 1)
+//             slot 0  (a0 | a0) x (b0 | 0 ) = a0b0             (0: the pack's zero tap 9)
+//   NPC = 3:  slot 2  (a1 | a2) x (b1 | b0) = a1b1 + a2b0
+//             slot 1  (a0 | a1) x (b2 | b0) = a0b2 + a1b0
+//             slot 0  (a0 | a0) x (b1 | b0) = a0b1 + a0b0      (tap 9 is not read)
+// split_apiece: the piece (16-B granule of the halo record) an A slot reads;
+// split_wrow: the row tap * NPC + piece of the chunk's weight slab a B slot reads.
+EV_DEVINL int split_apiece(int npc_, int s, int i, int hk) {
+  if (s < 4 || i == 0) return i;
+  if (npc_ == 2) return 1 - hk;
+  return i == 1 ? hk : 1 + hk;
+}
+EV_DEVINL int split_wrow(int npc_, int s, int i, int hk) {
+  if (s < 4) return (2 * s + hk) * npc_ + i;
+  if (npc_ == 2) return i == 0 ? (8 + hk) * 2 : 8 * 2 + hk;
+  return 8 * 3 + (i == 1 ? 2 - 2 * hk : 1 - hk);
+}
+
+// The MFMAs of k-step S over the fragment slots above: the terms of total order < NP,
+// smallest first, a0b0 last.  K-steps 0..3: NP (NP + 1) / 2 products of the two taps; k-step 4:
+// one MFMA per slot, NPC in all
+template <int NP, int S, int MF, int NF>
+EV_DEVINL void split_kstep_mfmas(bf16x8 (&a)[npc(NP)][MF], bf16x8 (&b)[npc(NP)][NF],
+                                 f32x16 (&acc)[MF][NF]) {
+  constexpr int NPC = npc(NP);
+#pragma unroll
+  for (int mf = 0; mf < MF; ++mf)
+#pragma unroll
+    for (int nf = 0; nf < NF; ++nf) {
+      if constexpr (S == 4) {
+#pragma unroll
+        for (int i = NPC - 1; i >= 0; --i) acc[mf][nf] = mfma_piece<NP>(a[i][mf], b[i][nf], acc[mf][nf]);
+      } else {
+        if constexpr (NP == 3) {
+          acc[mf][nf] = mfma_piece<NP>(a[1][mf], b[NPC - 2][nf], acc[mf][nf]);
+          acc[mf][nf] = mfma_piece<NP>(a[NPC - 1][mf], b[0][nf], acc[mf][nf]);
+          acc[mf][nf] = mfma_piece<NP>(a[0][mf], b[NPC - 1][nf], acc[mf][nf]);
+        }
+        acc[mf][nf] = mfma_piece<NP>(a[1][mf], b[0][nf], acc[mf][nf]);
+        acc[mf][nf] = mfma_piece<NP>(a[0][mf], b[1][nf], acc[mf][nf]);
+        acc[mf][nf] = mfma_piece<NP>(a[0][mf], b[0][nf], acc[mf][nf]);
+      }
+    }
+}
+
 // 16-B buffer load (32-bit byte offset; out-of-range offsets read 0 without a memory access)
 EV_DEVINL float4 bload4(__amdgpu_buffer_rsrc_t rs, int off) {
   return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0));
@@ -163,7 +217,7 @@ __global__ __launch_bounds__(NWV * 64, 2) void conv3x3_split_kernel(
     const int r = p / W, c = p - r * W;
     abase[mf] = r * WP + c;
   }
-  // this lane half's tap of k-step s (tap 9 reads tap 8's pixels; its weights are zero)
+  // this lane half's tap of k-step s (k-step 4: both halves read tap 8's pixels)
   int toff[5];
 #pragma unroll
   for (int s = 0; s < 5; ++s) {
@@ -274,37 +328,27 @@ __global__ __launch_bounds__(NWV * 64, 2) void conv3x3_split_kernel(
     }
     const char* lx = lx0 + cur * xslab;
     const char* lw = lw0 + cur * WSLAB;
-#pragma unroll
-    for (int s = 0; s < 5; ++s) {
+    auto kstep = [&](auto s_c) EV_LAMBDA_INLINE {
+      constexpr int s = decltype(s_c)::value;
       bf16x8 a[NP][MF], b[NP][NF];
 #pragma unroll
       for (int mf = 0; mf < MF; ++mf) {
         const char* pa = lx + (abase[mf] + toff[s]) * XPS;
 #pragma unroll
-        for (int i = 0; i < NP; ++i) a[i][mf] = lds_frag(pa + 16 * i);
+        for (int i = 0; i < NP; ++i) a[i][mf] = lds_frag(pa + 16 * split_apiece(NP, s, i, hk));
       }
-      const int t = 2 * s + hk;
 #pragma unroll
-      for (int nf = 0; nf < NF; ++nf) {
-        const char* pb = lw + ((t * NP) * NT + ncol + nf * 32) * 16;
+      for (int nf = 0; nf < NF; ++nf)
 #pragma unroll
-        for (int i = 0; i < NP; ++i) b[i][nf] = lds_frag(pb + i * NT * 16);
-      }
-      // terms of total order < NP, smallest first
-#pragma unroll
-      for (int mf = 0; mf < MF; ++mf)
-#pragma unroll
-        for (int nf = 0; nf < NF; ++nf) {
-          if (NP == 3) {
-            acc[mf][nf] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1][mf], b[NP - 2][nf], acc[mf][nf], 0, 0, 0);
-            acc[mf][nf] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[NP - 1][mf], b[0][nf], acc[mf][nf], 0, 0, 0);
-            acc[mf][nf] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0][mf], b[NP - 1][nf], acc[mf][nf], 0, 0, 0);
-          }
-          acc[mf][nf] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1][mf], b[0][nf], acc[mf][nf], 0, 0, 0);
-          acc[mf][nf] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0][mf], b[1][nf], acc[mf][nf], 0, 0, 0);
-          acc[mf][nf] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0][mf], b[0][nf], acc[mf][nf], 0, 0, 0);
-        }
-    }
+        for (int i = 0; i < NP; ++i)
+          b[i][nf] = lds_frag(lw + (split_wrow(NP, s, i, hk) * NT + ncol + nf * 32) * 16);
+      split_kstep_mfmas<NP, s>(a, b, acc);
+    };
+    kstep(std::integral_constant<int, 0>());
+    kstep(std::integral_constant<int, 1>());
+    kstep(std::integral_constant<int, 2>());
+    kstep(std::integral_constant<int, 3>());
+    kstep(std::integral_constant<int, 4>());
     if (more) store_halo(lx0 + nxt * xslab);
     __syncthreads();
   }
@@ -959,11 +1003,11 @@ __global__ __launch_bounds__(NWV * 64, (MODE == ACT_FIRST || pipe_wreg(NWV, WM, 
     const int nc = wn * NF * 32 + l32;   // this lane's output channel (B fragment column)
 #pragma unroll
     for (int s5 = 0; s5 < 5; ++s5) {
-      const int t = 2 * s5 + hk;
 #pragma unroll
       for (int i = 0; i < NPC; ++i)
-        wreg[sl][s5][i] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(
-                                                          rwp, ch * WSLAB + ((t * NPC + i) * NT + nc) * 16, 0, 0));
+        wreg[sl][s5][i] = __builtin_bit_cast(
+            bf16x8, __builtin_amdgcn_raw_buffer_load_b128(
+                        rwp, ch * WSLAB + (split_wrow(NPC, s5, i, hk) * NT + nc) * 16, 0, 0));
     }
   };
   auto issue_weights = [&](int it, char* lw) EV_LAMBDA_INLINE {
@@ -1045,19 +1089,17 @@ __global__ __launch_bounds__(NWV * 64, (MODE == ACT_FIRST || pipe_wreg(NWV, WM, 
       for (int mf = 0; mf < MF; ++mf) {
         const char* pa = lx + (abase[mf] + toff[s]) * XPS;
 #pragma unroll
-        for (int i = 0; i < NPC; ++i) a[i][mf] = lds_frag(pa + 16 * i);
+        for (int i = 0; i < NPC; ++i) a[i][mf] = lds_frag(pa + 16 * split_apiece(NPC, s, i, hk));
       }
       if constexpr (WREG) {
 #pragma unroll
         for (int i = 0; i < NPC; ++i) b[i][0] = wreg[WREG ? P : 0][WREG ? s : 0][i];
       } else {
-        const int t = 2 * s + hk;
 #pragma unroll
-        for (int nf = 0; nf < NF; ++nf) {
-          const char* pb = lw + ((t * NPC) * NT + ncol + nf * 32) * 16;
+        for (int nf = 0; nf < NF; ++nf)
 #pragma unroll
-          for (int i = 0; i < NPC; ++i) b[i][nf] = lds_frag(pb + i * NT * 16);
-        }
+          for (int i = 0; i < NPC; ++i)
+            b[i][nf] = lds_frag(lw + (split_wrow(NPC, s, i, hk) * NT + ncol + nf * 32) * 16);
       }
     };
     if constexpr (FPF) load_frags(0, fa[0], fb[0]);
@@ -1071,19 +1113,7 @@ __global__ __launch_bounds__(NWV * 64, (MODE == ACT_FIRST || pipe_wreg(NWV, WM, 
       }
       bf16x8 (&a)[NPC][MF] = fa[fs_];
       bf16x8 (&b)[NPC][NF] = fb[fs_];
-#pragma unroll
-      for (int mf = 0; mf < MF; ++mf)
-#pragma unroll
-        for (int nf = 0; nf < NF; ++nf) {
-          if constexpr (NP == 3) {
-            acc[mf][nf] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1][mf], b[NP - 2][nf], acc[mf][nf], 0, 0, 0);
-            acc[mf][nf] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[NP - 1][mf], b[0][nf], acc[mf][nf], 0, 0, 0);
-            acc[mf][nf] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0][mf], b[NP - 1][nf], acc[mf][nf], 0, 0, 0);
-          }
-          acc[mf][nf] = mfma_piece<NP>(a[1][mf], b[0][nf], acc[mf][nf]);
-          acc[mf][nf] = mfma_piece<NP>(a[0][mf], b[1][nf], acc[mf][nf]);
-          acc[mf][nf] = mfma_piece<NP>(a[0][mf], b[0][nf], acc[mf][nf]);
-        }
+      split_kstep_mfmas<NP, s>(a, b, acc);
       // staging of it+1, spread over the k-steps (PD = 1: its loads were issued this
       // iteration, so stage after the last k-step's MFMAs are queued); every item is staged
       // (dead ones load nothing and write the dummy record), so the region has no branch
