@@ -123,6 +123,7 @@ SIGNATURES = {
     "ebsdvae_kernel_misorientation": [P, I, I, I, ctypes.c_double, P, P],
     "ebsdvae_grain_work": [I, I],
     "ebsdvae_segment_grains": [P, P, I, I, I, ctypes.c_double, P, P, P, P, P, P, P],
+    "ebsdvae_simulate_patterns": [P, P, I, P, P, I, I, I, I, P, P],
 }
 _RESTYPE = {"ebsdvae_last_error": ctypes.c_char_p, "ebsdvae_wgrad_reduce_work": ctypes.c_size_t,
             "ebsdvae_wgrad_reduce_batch_work": ctypes.c_size_t,
@@ -142,7 +143,7 @@ QUERIES = {"ebsdvae_version", "ebsdvae_conv_first_stat_tiles", "ebsdvae_conv3x3_
            "ebsdvae_conv3x3_dwgrad_slices", "ebsdvae_conv3x3_dwgrad_stat_tiles"}
 
 # include/ebsdvae.h EBSDVAE_ABI_VERSION: the signatures above
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 _lib = None
 _lock = threading.Lock()

@@ -22,7 +22,9 @@ Same public names, constructor arguments and behaviour as the reference:
 
 The batched transform itself (`ingest_patterns`) and the stages beyond the reference
 (background correction, detector binning, neighbour averaging, `index_scan`'s per-scan plan)
-live in `latice.patterns`; every public name of theirs is re-exported here.
+live in `latice.patterns`; every public name of theirs is re-exported here.  So are those of
+`latice.simulation`, the dictionary side's counterpart: dictionary patterns projected from a
+master pattern on the device (`MasterPattern`, `DetectorGeometry`, `simulate_patterns`).
 
 Lightning is optional: DPDataModule subclasses `pl.LightningDataModule` when
 pytorch_lightning is importable.  There is no CPU fallback: the transform runs on the ROCm
@@ -46,6 +48,7 @@ from .patterns import (MAX_CORRECTED_SIDE, MAX_NEIGHBOUR_SIDE, MAX_RESAMPLE_FACT
                        average_neighbour_range, check_resampled_correction, correct_patterns,
                        gaussian_taps, ingest_patterns, ingest_patterns_u8, neighbour_window,
                        nlpar_patterns, nlpar_range, nlpar_weights, resample_axis, resample_denominator, resample_patterns)
+from .simulation import DetectorGeometry, MasterPattern, simulate_patterns  # noqa: F401
 
 try:  # pragma: no cover - depends on the environment
     import pytorch_lightning as pl

@@ -30,6 +30,9 @@ path: same `IndexerConfig` and `DiffractionPatternIndexer` API and call contract
   `maps=ScanMaps(...)` appends the scan maps (latice/index/maps.py, csrc/scan_maps.hip: IPF
   colours, orientation similarity, kernel average misorientation), built from the result rows
   behind the last batch, to the same result buffer and the same single copy back.
+* `build_dictionary_from_master` has no counterpart either: the dictionary patterns are projected
+  from a master pattern on the device, batch by batch, in front of `encode_mu`
+  (latice/simulation.py, csrc/simulate.hip); only the orientation list is uploaded.
 """
 from __future__ import annotations
 
@@ -53,7 +56,10 @@ from latice.index.scan import (SCAN_F32, SCAN_F64, SCAN_U8, ScanIndexResult, nei
                                open_scan, scan_batches, scan_dtype_code)
 from latice.model import VariationalAutoEncoder
 from latice.patterns import (NLPAR, DetectorResample, NeighbourAverage, PatternCorrection,
-                             ScanIngest, accumulate_patterns, average_neighbour_range, nlpar_range)
+                             ScanIngest, accumulate_patterns, average_neighbour_range,
+                             correct_patterns, nlpar_range)
+from latice.simulation import (DetectorGeometry, MasterPattern, check_dictionary_request,
+                               simulate_patterns)
 
 logger = logging.getLogger(__name__)
 
@@ -222,6 +228,50 @@ class DiffractionPatternIndexer:
         latent_vectors, orientations = self._extract_latent_vectors_with_angles(data_module)
         logger.info(f"Adding {len(latent_vectors)} vectors to database")
         self.db.add_vectors(latent_vectors, orientations)
+
+    def build_dictionary_from_master(self, master: MasterPattern, orientations,
+                                     detector: DetectorGeometry | None = None,
+                                     batch_size: int | None = None,
+                                     correction: PatternCorrection | None = None) -> None:
+        """The dictionary of `orientations` ((N, 3) float64 host array, Bunge angles in degrees)
+        simulated from `master` on the device instead of read from a pattern file; the reference
+        has no counterpart.  `detector` defaults to `DetectorGeometry(config.image_size)` and must
+        have the model's image size.  The orientation list is uploaded once; per batch one
+        `simulate_patterns` launch fills a reused batch buffer, `model.encode_mu` reads it and the
+        latents go into their rows of one (N, d) device tensor; one `db.add_vectors(latents,
+        orientations)` follows the last batch.  Nothing inside the loop waits for the device and
+        no pattern ever leaves it.
+
+        With `correction` (a `PatternCorrection` without a static background, which belongs to a
+        detector) every batch is simulated without the rescale and passes through
+        `correct_patterns` at equal size: the dynamic background step and the rescale of the
+        experimental side.  Everything is checked (ValueError) before the device is touched."""
+        ori, detector, batch_size = check_dictionary_request(
+            self.config.image_size, master, orientations, detector,
+            batch_size or self.config.batch_size, correction)
+        if self.device.type != "cuda":
+            raise RuntimeError("build_dictionary_from_master needs a ROCm device (no CPU fallback)")
+        n, dev = ori.shape[0], self.device
+        h, w = detector.shape
+        logger.info(f"Simulating and encoding {n} dictionary patterns from a master pattern")
+        with torch.cuda.device(dev):
+            ori_dev = torch.from_numpy(ori).to(dev)
+            x = torch.empty(min(batch_size, n), 1, h, w, dtype=torch.float32, device=dev)
+            y = torch.empty_like(x) if correction is not None else None
+            latents = None
+            for s in range(0, n, batch_size):
+                m = min(batch_size, n - s)
+                simulate_patterns(master, ori_dev[s:s + m], detector, rescale=correction is None,
+                                  out=x[:m])
+                xb = x[:m]
+                if correction is not None:
+                    xb = correct_patterns(x[:m].view(m, h, w), (h, w), correction, dev, out=y[:m])
+                mu = self.model.encode_mu(xb)
+                if latents is None:
+                    latents = torch.empty(n, mu.shape[1], dtype=torch.float32, device=dev)
+                latents[s:s + m].copy_(mu)
+        logger.info(f"Adding {n} vectors to database")
+        self.db.add_vectors(latents, ori)
 
     def encode_pattern(self, pattern) -> np.ndarray:
         """dp_indexer.py:113-136."""

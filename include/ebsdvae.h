@@ -40,9 +40,10 @@ const char* ebsdvae_last_error(void);
  * incompatible signature change (2: ebsdvae_heads_fwd / _bwd / ebsdvae_latent_mu take a
  * caller-owned `work` scratch pointer; 3: the scan maps, ebsdvae_ipf_colors /
  * ebsdvae_orientation_similarity / ebsdvae_kernel_misorientation, which the binding requires;
- * 4: the grains, ebsdvae_grain_work / ebsdvae_segment_grains, which the binding requires).
+ * 4: the grains, ebsdvae_grain_work / ebsdvae_segment_grains, which the binding requires;
+ * 5: the dictionary simulation, ebsdvae_simulate_patterns, which the binding requires).
  * Callers must check it before the first call. */
-#define EBSDVAE_ABI_VERSION 4
+#define EBSDVAE_ABI_VERSION 5
 int ebsdvae_version(void);
 
 /* ---- stream ordering ------------------------------------------------------------------
@@ -785,6 +786,44 @@ int ebsdvae_segment_grains(const double* euler, const int* valid, int rows, int 
                            int connectivity, double threshold_deg, int* grain_id,
                            double* grain_euler, float* gos, float* grod, unsigned char* boundary,
                            void* work, ebsdvae_stream_t stream);
+
+/* ---- dictionary simulation ("Dictionary simulation") -------------
+ * Dictionary patterns projected from a master pattern: dst (B, 1, h, w) float32, 1 <= h, w <= 256,
+ * one launch, no scratch, no atomics.  master_upper / master_lower are the (M, M) float32 square
+ * Lambert projections of the upper (z >= 0) and lower hemisphere, M = 2n + 1 odd, 3 <= M <= 4097;
+ * the two pointers may be equal (a centrosymmetric master).  dirs is planar (3, h w) float32: the
+ * unit direction of every detector pixel in the sample frame, row-major pixel order, used as
+ * given (neither built nor normalised here).  euler is (B, 3) float64, 8-byte aligned, Bunge
+ * angles phi1, Phi, phi2 in degrees.  Per pattern and pixel, every float32 operation below rounding once (no
+ * contraction beyond the fma's written out):
+ *  (a) g, the Bunge passive matrix (sample -> crystal), formed in float64 from the float64 sines
+ *      and cosines c1, s1, c, s, c2, s2 of phi1, Phi, phi2 (each angle times pi / 180) and rounded
+ *      to float32:
+ *        g = [[ c1 c2 - s1 s2 c,   s1 c2 + c1 s2 c,  s2 s ],
+ *             [-c1 s2 - s1 c2 c,  -s1 s2 + c1 c2 c,  c2 s ],
+ *             [ s1 s,             -c1 s,             c    ]]
+ *      (scipy's Rotation.from_euler("ZXZ", e, degrees=True).inv().as_matrix(); NOT the extrinsic
+ *      "zxz" reading of ebsdvae_orient_consensus, which the same triples get there);
+ *  (b) v = g d: v_i = fma(g_i2, d_z, fma(g_i1, d_y, g_i0 * d_x));
+ *  (c) with (x, y, z) = v: the lower hemisphere iff z < 0;
+ *      s = sqrt(fma(x, x, y * y) / (1 + |z|)); k = float32(4 / pi);
+ *        x == 0 && y == 0:  tx = ty = 0;
+ *        |y| <= |x|:        tx = copysign(s, x), ty = tx * (k * atan(y / x));
+ *        otherwise:         ty = copysign(s, y), tx = ty * (k * atan(x / y));
+ *  (d) column u = min(max(fma(n, tx, n), 0), 2n), j0 = min(int(u), 2n - 1), fu = u - j0; row r,
+ *      r0, fr the same from ty; with m the chosen hemisphere,
+ *        top = fma(fu, m[r0][j0 + 1] - m[r0][j0], m[r0][j0]),
+ *        bot = fma(fu, m[r0 + 1][j0 + 1] - m[r0 + 1][j0], m[r0 + 1][j0]),
+ *        value = fma(fr, bot - top, top);
+ *  (e) rescale 0: the value; rescale 1: (value - lo) / (hi - lo) with lo, hi the pattern's
+ *      minimum and maximum, 0 everywhere when hi == lo (ebsdvae_correct_patterns' rule).
+ * A pattern's output depends on its own Euler triple, dirs and the master only: any split of a
+ * batch gives the same bytes.  Nonzero, and nothing launched or written, for a null pointer, M
+ * even or outside 3..4097, h or w outside 1..256, B < 0 or rescale outside 0..1; B == 0 returns 0
+ * and launches nothing. */
+int ebsdvae_simulate_patterns(const float* master_upper, const float* master_lower, int M,
+                              const float* dirs, const double* euler, int B, int h, int w,
+                              int rescale, float* dst, ebsdvae_stream_t stream);
 
 #ifdef __cplusplus
 }
